@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
-"""bench.py -- the hot path of BASELINE.json on MI355X: TAF encode (Mevents/s) + roofline + CPU baseline, then the other
-rows of SURVEY.md section 8(d): GEN1-shaped and batched encodes, Event Volume, detector forward, train step.
+"""bench.py -- the hot path of BASELINE.json on MI355X: TAF encode (Mevents/s) + roofline; with --full also the CPU baseline,
+the copy rate, the general path and the other rows of SURVEY.md section 8(d): GEN1-shaped and batched encodes, Event Volume,
+detector forward, train step.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload taf_mpx|taf_gen1] [--hotspot]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload taf_mpx|taf_gen1] [--hotspot] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps of the headline encode and prints the line; everything else it reports
+(`roofline.frac_of_copy`, `general_path`, `cpu_baseline`, `also` / `gen1`, `detector`, `train`, `stripe_sharding`) needs --full.
+--dump-outputs DIR writes what the last timed step handed its caller (rank 0): DIR/taf_u8.npy, the uint8 volume in full as
+float32, and DIR/taf_state_sample.npy, a fixed seeded sample of the FIFO state it updated in place (DUMP_STATE_SAMPLE floats).
 
 A step = one pass of the TAF encoder over one batch of synthetic DAT records already resident in HBM: SURVEY.md 8(d)
 cfg 3 -- seed 1003, 10 M events, 1280x720 native, 8 windows x 10 ms, K = 8, leaky transform + uint8 output, FIFO state
@@ -242,6 +248,8 @@ TOP_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 CONFIG_KEYS = ("workload", "path", "parallelism", "detail")
 LINE_LIMIT = 6000
 DETAIL_FILE = "bench_detail.json"
+DUMP_STATE_SAMPLE = 1 << 20  # the uint8 volume in full (59 MB as float32 at 1280x720) + 4 MB of the state: <= 64 MB in all
+DUMP_SEED = 1003
 
 
 def _short(v, n):
@@ -309,6 +317,18 @@ def emit(result, out, write_detail=True):
         print("bench.py detail: " + json.dumps(result), file=sys.stderr, flush=True)
     print(text, file=out, flush=True)
     return line
+
+
+def dump_outputs(path, torch, u8, state):
+    """--dump-outputs: the uint8 volume the last timed step returned, in full (as float32: exact), and the FIFO state it
+    updated in place, as the same seeded sample of DUMP_STATE_SAMPLE elements in every run (all of it when smaller)."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "taf_u8.npy"), u8.cpu().numpy().astype(np.float32))
+    flat = state.reshape(-1)
+    n = flat.numel()
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_STATE_SAMPLE, replace=False)) if n > DUMP_STATE_SAMPLE \
+        else np.arange(n)
+    np.save(os.path.join(path, "taf_state_sample.npy"), flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy())
 
 
 def fast_kernel_label(er=None):
@@ -457,6 +477,11 @@ def main():
     ap.add_argument("--no-also", action="store_true", help="skip the other encoder workloads (clean per-kernel profiles)")
     ap.add_argument("--train-batch", type=int, default=64, help="per-GPU batch of the train-step leg")
     ap.add_argument("--local_rank", "--local-rank", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs beside the headline: copy rate, general path, CPU baselines, other encoder rows, "
+                         "detector, train step, stripe sharding at N > 1 (the --no-* flags above select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/*.npy (rank 0)")
     args = ap.parse_args()
     if args.gpus is None:
         args.gpus = int(os.environ.get("WORLD_SIZE", "1"))
@@ -491,7 +516,7 @@ def main():
     if not fast_ok:  # (never seen on gfx950; the batched rows have no general-path form)
         args.no_also = True
     timer = Timer(torch, fd, er)
-    copy_gbs = copy_bandwidth(torch)
+    copy_gbs = copy_bandwidth(torch) if args.full else None
 
     seed, n, H, W, t_span, n_win, win_us, K = WORKLOADS[args.workload]
     ev = synth.synth_events(seed + 7919 * rank, n, W, H, t_span, hotspot=args.hotspot)
@@ -499,10 +524,11 @@ def main():
     dat = torch.from_numpy(dat_h.view(np.uint8).reshape(-1, 8)).cuda()
     state = torch.full((H, W, 2, K), -6000.0, device="cuda")
     use_fast = n >= er.FAST_MIN_EVENTS and fast_ok
+    last = {}
 
     def step(fast=use_fast):
-        return er.encode_taf_dat(dat, (H, W), state, 0, win_us, n_win, K, want_view=False, want_u8=True, flip_k=True,
-                                 check=False, fast=fast)
+        last["u8"], _ = er.encode_taf_dat(dat, (H, W), state, 0, win_us, n_win, K, want_view=False, want_u8=True, flip_k=True,
+                                          check=False, fast=fast)
 
     # correctness guard: data-dependent status of the first encode must be clean (and the fast path must have taken it)
     if use_fast:
@@ -510,6 +536,8 @@ def main():
     else:
         er.encode_taf_dat(dat, (H, W), state, 0, win_us, n_win, K, check=True, fast=False)
     per_step, dev_ms = timer.run(step, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, last.pop("u8"), state)
     alg_bytes = taf_algorithmic_bytes(n, H, W, K)
     kernels = fast_kernel_label(er) if use_fast else \
         "frlw_taf_encode = k_hist + k_slabscan + k_tilescan + k_scatter + k_taf_tile (dominant: k_taf_tile)"
@@ -538,13 +566,13 @@ def main():
         "roofline": roofline(alg_bytes, dev_ms, kernels, copy_gbs, f"{n} events"),
     }
     attach_traffic(result["roofline"], f"{args.workload}{'_hotspot' if args.hotspot else ''}")
-    if use_fast:  # the general path on the same workload, for comparison
+    if use_fast and args.full:  # the general path on the same workload, for comparison
         st2 = state.clone()
         per2, dev2 = timer.run(lambda: er.encode_taf_dat(dat, (H, W), st2, 0, win_us, n_win, K, check=False, fast=False),
                                max(5, args.steps // 5), 2)
         result["general_path"] = {"value": round(n_gpus * n / per2 / 1e6, 2), "unit": "Mevents/s", "device_ms": round(dev2, 4)}
 
-    if world > 1 and args.workload == "taf_mpx":
+    if args.full and world > 1 and args.workload == "taf_mpx":
         # SURVEY.md 8(e), second form: ONE stream sharded spatially -- every rank holds the same 10 M-event stream and encodes its
         # stripe of rows (events routed by y on the device, own stripe of state / output); the only exchange is the OR of the
         # 64-bit window masks (generate_taf.py:40-41 is a per-frame rule) between the two halves of the encode.  Strong scaling
@@ -561,7 +589,7 @@ def main():
                                      "value": round(n / per_s / 1e6, 2), "unit": "Mevents/s", "ms_per_step": round(per_s * 1e3, 4),
                                      "rows_of_rank0": [lo, hi]}
         del dat_s, st_s
-    if args.workload == "taf_mpx" and not args.no_also:
+    if args.full and args.workload == "taf_mpx" and not args.no_also:
         result["also"] = bench_also(args, torch, synth, er, timer, rank, n_gpus, copy_gbs)
         # the shape BASELINE.json's metric names (GEN1 304x240), promoted: a block of its own and a compact copy inside
         # `roofline` (the keys the driver keeps when it parses the line)
@@ -594,7 +622,7 @@ def main():
         result["roofline"]["general_path_ms"] = result["general_path"]["device_ms"]
     if "stripe_sharding" in result:
         result["roofline"]["stripe_ms"] = result["stripe_sharding"]["ms_per_step"]
-    if not args.no_detector:
+    if args.full and not args.no_detector:
         result["detector"] = bench_detector(args, torch, world, rank, timer)
         d = result["detector"]  # the second half of BASELINE.json's metric, in the keys the driver keeps (scalars)
         flat = result["roofline"]
@@ -620,7 +648,7 @@ def main():
             flat["detector_1mpx_frac"] = d["shape_1mpx"]["roofline"]["frac"]
             flat["detector_1mpx_ms_per_batch"] = d["shape_1mpx"]["ms_per_batch"]
             flat["detector_1mpx_fwd_nms_ms"] = d["shape_1mpx"].get("fwd_plus_decode_nms_ms")
-    if not args.no_train:
+    if args.full and not args.no_train:
         try:
             result["train"] = bench_train(args, torch, world, rank, local_rank, timer)
             t = result["train"]
@@ -653,7 +681,7 @@ def main():
                 flat["global64_ms"] = t["global64"]["ms_per_step"]
         except Exception as e:  # never lose the headline line to the extra leg
             result["train"] = {"error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline_taf(dat_h, n, H, W, K, n_win, win_us)
     if rank == 0:
         emit(result, out)

@@ -7,6 +7,8 @@ import io
 import json
 import os
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -152,3 +154,72 @@ def test_headline_kernel_label_names_the_chunk_major_kernels():
     for name in ("kf_scatter_cm", "kf_split_whole", "kf_segcount_cm", "kf_split_place", "kf_taf_walk"):
         assert name in label
     assert "kf_hist" not in label and "kf_tilescan" not in label
+
+
+def test_dump_outputs_are_float32_within_64_mb_and_sample_the_same_state_elements(tmp_path):
+    """--dump-outputs at the headline shape: the uint8 volume in full (exact as float32) and the same seeded sample of the
+    state in every run, together at most 64 MB."""
+    import numpy as np
+    import torch
+    b = _bench()
+    H, W, K = 720, 1280, 8
+    u8 = torch.from_numpy(np.random.default_rng(1).integers(0, 256, size=(K, 2, H, W), dtype=np.uint8))
+    state = torch.arange(H * W * 2 * K, dtype=torch.float32).reshape(H, W, 2, K)  # value = flat index (exact below 2^24)
+    runs = []
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), torch, u8, state)
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == ["taf_state_sample.npy", "taf_u8.npy"]
+        assert sum(os.path.getsize(tmp_path / d / f) for f in files) <= 64_000_000
+        runs.append({f: np.load(tmp_path / d / f) for f in files})
+    got_u8, sample = runs[0]["taf_u8.npy"], runs[0]["taf_state_sample.npy"]
+    assert got_u8.dtype == np.float32 and got_u8.shape == (K, 2, H, W) and np.array_equal(got_u8, u8.numpy())
+    assert sample.dtype == np.float32 and sample.shape == (b.DUMP_STATE_SAMPLE,)
+    assert np.all(np.diff(sample) > 0) and sample[-1] < state.numel()  # distinct elements of the state, in order
+    assert np.array_equal(sample, runs[1]["taf_state_sample.npy"])
+    small = torch.arange(1000, dtype=torch.float32)
+    b.dump_outputs(str(tmp_path / "c"), torch, u8[:1], small)
+    assert np.array_equal(np.load(tmp_path / "c" / "taf_state_sample.npy"), small.numpy())  # all of a small state
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    """``bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR``: the line reports those 3 steps and none of the --full legs,
+    and DIR holds the last step's outputs -- the state bit for bit what the CPU oracle makes of the same 1 + 1 + 3 encodes
+    (the checked first call, the warm-up, the timed steps), the uint8 volume within 1 LSB of it."""
+    import subprocess
+    import sys
+    import numpy as np
+    torch = pytest.importorskip("torch")
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    dump = tmp_path / "out"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    assert p.stdout.count("\n") == 1
+    line = json.loads(p.stdout)
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert (line["metric"], line["unit"], line["higher_is_better"], line["dtype"]) == \
+        ("TAF encode throughput (Mevents/s)", "Mevents/s", True, "f32")
+    assert "cpu_baseline" not in line
+    for k in ("frac_of_copy", "detector_frames_per_s", "train_ms", "gen1_taf_single_graph_ms"):
+        assert line["roofline"][k] is None, k
+    assert "general_path_ms" not in line["roofline"]
+
+    b = _bench()
+    from frlw_evd_amd import synth
+    from oracle import oracle as orc
+    seed, n, H, W, t_span, n_win, win_us, K = b.WORKLOADS["taf_mpx"]
+    dat = synth.to_dat8(synth.synth_events(seed, n, W, H, t_span))
+    st = np.full((H, W, 2, K), -6000, np.float32)
+    for _ in range(1 + 1 + 3):
+        view, st = orc.taf_stream_dat8(dat, (H, W), (H, W), K, 0, win_us, n_win, st)
+    want_u8 = orc.quantize_u8(np.ascontiguousarray(orc.leaky_transform(view.reshape(K, 2, H, W))[::-1]))
+    got_u8 = np.load(dump / "taf_u8.npy")
+    assert got_u8.dtype == np.float32 and got_u8.shape == want_u8.shape
+    diff = np.abs(got_u8 - want_u8.astype(np.float32))
+    assert diff.max() <= 1 and int((diff != 0).sum()) <= max(1, int(1e-5 * diff.size))
+    idx = np.sort(np.random.default_rng(b.DUMP_SEED).choice(st.size, b.DUMP_STATE_SAMPLE, replace=False))
+    got_st = np.load(dump / "taf_state_sample.npy")
+    assert got_st.dtype == np.float32 and got_st.tobytes() == st.reshape(-1)[idx].tobytes()

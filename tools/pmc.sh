@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 run() { # name counters...
   local name=$1; shift
   rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$OUT/$name" -o pmc -- \
-      python3 "$R/bench.py" --steps 4 --warmup 1 --no-cpu-baseline ${EXTRA:-} > "$OUT/$name.log" 2>&1
+      python3 "$R/bench.py" --full --steps 4 --warmup 1 --no-cpu-baseline ${EXTRA:-} > "$OUT/$name.log" 2>&1
   echo "$name rc=$?"
 }
 run sq1 SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_BUSY_CYCLES

@@ -11,7 +11,7 @@ KEEP=$R/gpurun_out/prof_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT" "$KEEP"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o trace -- \
-    python3 "$R/bench.py" --steps 20 --warmup 3 --no-cpu-baseline "$@" > "$OUT/bench.log" 2>&1
+    python3 "$R/bench.py" --full --steps 20 --warmup 3 --no-cpu-baseline "$@" > "$OUT/bench.log" 2>&1
 echo "rc=$?"; tail -3 "$OUT/bench.log"
 find "$OUT" -name "*kernel_stats.csv" | head -3
 F=$(find "$OUT" -name "*kernel_stats.csv" | head -1)

@@ -10,8 +10,8 @@ stats() { # tag program args...   (the program itself behind `--`: no shell, no 
   rocprofv3 --kernel-trace --stats --output-format csv -d $O -o t -- "$@" > $O/run.log 2>&1; echo "$tag rc=$?"
   cp "$(find $O -name '*kernel_stats.csv' | head -1)" $K/${tag}_kernel_stats.csv
 }
-stats bench python3 $R/bench.py --steps 20 --warmup 3 --no-also --no-detector --no-train --no-cpu-baseline
-stats hot python3 $R/bench.py --steps 10 --warmup 2 --hotspot --no-also --no-detector --no-train --no-cpu-baseline
+stats bench python3 $R/bench.py --full --steps 20 --warmup 3 --no-also --no-detector --no-train --no-cpu-baseline
+stats hot python3 $R/bench.py --full --steps 10 --warmup 2 --hotspot --no-also --no-detector --no-train --no-cpu-baseline
 for c in gen1 gen1x64 ev1 evb1 evb64 small; do stats lab_$c $R/build/enc_lab $LIB --cfg $c --reps 20; done
 stats lab_gen1_nocm $R/build/enc_lab $LIB --cfg gen1 --reps 20 --no-cm # ... and the histogram partition on one GEN1 stream
 stats lab_evb64_nocm $R/build/enc_lab $LIB --cfg evb64 --reps 20 --no-cm
@@ -49,6 +49,6 @@ python3 $R/tools/time_wtab.py 2>&1 | grep -v amdgpu.ids > $K/wtab_ab.txt
 HOT=1 python3 $R/tools/time_wtab.py 2>&1 | grep -v amdgpu.ids > $K/wtab_ab_hot.txt
 CFG=gen1x64 python3 $R/tools/time_wtab.py 2>&1 | grep -v amdgpu.ids > $K/wtab_ab_gen1x64.txt
 (cd $R && bash tools/pmc_clock_bin.sh build/conv_lab 32 20 2 > $K/conv_big_clock.txt 2>&1); cd /tmp
-cd $R && python3 bench.py > $K/bench.json 2> $K/bench.err; echo "bench rc=$?"; cp bench_detail.json $K/bench_detail.json
-python3 bench.py --hotspot --no-detector --no-train --no-also --no-cpu-baseline > $K/bench_hotspot.json 2>> $K/bench.err; echo "bench hot rc=$?"
+cd $R && python3 bench.py --full > $K/bench.json 2> $K/bench.err; echo "bench rc=$?"; cp bench_detail.json $K/bench_detail.json
+python3 bench.py --full --hotspot --no-detector --no-train --no-also --no-cpu-baseline > $K/bench_hotspot.json 2>> $K/bench.err; echo "bench hot rc=$?"
 ls -la $K
