@@ -8,7 +8,7 @@ Data: with ``--bbox_path`` / ``--data_path`` the pre-encoded ``uint8`` files of 
 ``frlw_evd_amd.dataset`` (the reference's dataset classes and ``Loader``: uint8 batches over PCIe, the sample transform as
 one kernel on the GPU).  A run without them draws SYNTHETIC event streams and encodes them on the GPU every step
 (``e2e.SyntheticTafSource``), which is BASELINE.json's config 5.  The evaluator hand-off is the real one
-(``frlw_evd_amd.evaluator``); COCO mAP needs pycocotools and is reported only when a ``metric_fn`` is injected.
+(``frlw_evd_amd.evaluator``); ``--metric coco`` scores it with the GPU COCO mAP of ``frlw_evd_amd.coco_eval``.
 """
 from __future__ import annotations
 
@@ -71,7 +71,10 @@ class basicExp:
         self.nr_input_channels = int(2 * self.settings.event_volume_bins)
         self.input_layer = Focus
         self.synthetic_batches = int(os.environ.get("FRLW_SYNTHETIC_BATCHES", "4"))  # batches per synthetic epoch
-        self.metric_fn = None  # inject evaluate_detection (pycocotools) to get mAP out of .test()
+        self.metric_fn = None  # --metric coco: the GPU COCO scorer (coco_eval.evaluate_detection); else the paired lists
+        if getattr(settings, "metric", "none") == "coco":
+            from . import coco_eval
+            self.metric_fn = coco_eval.evaluate_detection
 
     # ---- data -------------------------------------------------------------------------------------------
     def _classes(self):
@@ -278,7 +281,7 @@ class basicExp:
 
     def validationEpoch(self, result):
         eval_results = self.testingEpoch(result)
-        score = eval_results[0] if isinstance(eval_results, (list, tuple)) else 0.0  # mAP needs an injected metric_fn
+        score = eval_results[0] if isinstance(eval_results, (list, tuple)) else 0.0  # mAP with --metric coco
         if score > self.max_score or not os.path.exists(os.path.join(self.settings.ckpt_dir, "best_epoch.pth")):
             self.max_score = max(self.max_score, score)
             if self.settings.local_rank == 0:

@@ -488,6 +488,21 @@ int frlw_eval_transform_dt(const float *dets, const int32_t *img_of_row, const i
                            float rh, float skip_ts, float min_diag_sq, float min_w, float min_h, float *out,
                            uint8_t *keep, frlw_stream_t stream);
 
+/* COCO bounding-box mAP (evaluate/src/metrics/coco_eval.py:89-113: pycocotools COCOeval, iouType 'bbox', default
+ * params, no crowd annotations) of n_img images ("windows") and n_cls categories (frlw-evd_amd/coco_eval.py packs them).
+ * Ground truths of image i are rows gt_off[i] .. gt_off[i+1]-1 (gt_off[n_img] = n_gt), detections likewise with dt_off:
+ * box (n, 4) double [x, y, w, h], area double (w * h in the row's own dtype, widened), class int32 in [0, n_cls) (rows of
+ * other classes are dropped by the caller), score double.  iou_thrs[10] = np.linspace(.5, .95, 10) and
+ * rec_thrs[101] = np.linspace(0, 1, 101) as pycocotools builds them.  Outputs (device, float64, C order):
+ * precision (10, 101, n_cls, 4, 3) and recall (10, n_cls, 4, 3), = COCOeval.eval['precision'] / ['recall'] bit for bit.
+ * 1 <= n_cls <= 254, n_dt < 2^31.  Bad sizes: FRLW_ERR_ARG; workspace below frlw_coco_workspace_bytes(): FRLW_ERR_WORKSPACE.
+ * The workspace query is host arithmetic only (0 for sizes the evaluator refuses). */
+int64_t frlw_coco_workspace_bytes(int64_t n_img, int64_t n_gt, int64_t n_dt, int n_cls);
+int frlw_coco_eval(const double *gt_box, const double *gt_area, const int32_t *gt_cls, const int64_t *gt_off, int64_t n_gt,
+                   const double *dt_box, const double *dt_area, const double *dt_score, const int32_t *dt_cls,
+                   const int64_t *dt_off, int64_t n_dt, int n_img, int n_cls, const double *iou_thrs, const double *rec_thrs,
+                   void *workspace, int64_t workspace_bytes, double *precision, double *recall, frlw_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Training-mode BaseConv = Conv2d(bias=False) + BatchNorm2d(batch statistics) + SiLU
  * (core/yolox/models/network_blocks.py:33-65) for the train step of core/exp.py:283-315: forward, data gradient,

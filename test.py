@@ -26,6 +26,7 @@ def build_parser():
     parser.add_argument("--batch_size", type=int, default=1)
     parser.add_argument("--num_cpu_workers", type=int, default=-1)
     parser.add_argument("--nodes", type=int, default=1)
+    parser.add_argument("--metric", choices=("none", "coco"), default="none")  # coco: score the test split with the GPU COCO mAP
     return parser
 
 
@@ -37,11 +38,22 @@ def main(argv=None):
     from frlw_evd_amd.settings import Setting_test
     settings = Setting_test(args)
     tester = cls(settings)
+    stats = []
+    if settings.metric == "coco":  # evaluate/evaluator.py:103-113: the COCO summary, then the score
+        from frlw_evd_amd import coco_eval
+
+        def metric_fn(gt_boxes_list, dt_boxes_list, **kw):
+            stats.append(coco_eval.coco_eval_arrays(gt_boxes_list, dt_boxes_list, **kw)[2])
+            return tuple(float(s) for s in stats[-1][:6])
+        tester.metric_fn = metric_fn
     result = tester.test()
     import torch
     if torch.distributed.get_rank() == 0 and isinstance(result, dict):
         n_dt = sum(len(d) for d in result["dt_boxes_list"])
         print({"images": len(result["gt_boxes_list"]), "detections": n_dt, "avg_infer_ms": round(result["avg_infer_ms"], 3)})
+    if torch.distributed.get_rank() == 0 and stats:
+        coco_eval.summarize(stats[-1])
+        print("Current score: ", result[0])
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
     return result

@@ -34,6 +34,7 @@ def build_parser():
     parser.add_argument("--num_cpu_workers", type=int, default=-1)
     parser.add_argument("--nodes", type=int, default=1)  # number of GPUs
     parser.add_argument("--augmentation", type=bool, default=True)  # (any non-empty string is True, like the reference)
+    parser.add_argument("--metric", choices=("none", "coco"), default="none")  # coco: score validation with the GPU COCO mAP
     return parser
 
 
