@@ -20,6 +20,11 @@ FRLW_ERR_UNSUPPORTED = -6
 FRLW_ERR_SPAN = -7
 MAX_SEQUENCES = 64
 
+# the FRLW_CONV_PATH_* counters of frlw_conv_path_counts, in the header's enum order (lower case, prefix dropped)
+CONV_PATHS = ("128x32", "128x128_4x1", "128x128_2x2", "64x128", "64x64", "split_vec", "split_scalar", "split_inkernel",
+              "split_inkernel_stats", "gathered", "half_batch", "parity", "wgrad_128x128", "wgrad_128x32", "wgrad_128x64",
+              "wgrad_64x64", "wgrad_group_sum", "wgrad_scratch_limited")
+
 LAYOUT_XYTP_F64 = 0
 LAYOUT_DAT8 = 1
 TAF_U8_FLIP_K = 1
@@ -132,6 +137,7 @@ SYMBOLS = {
                                    _P, _P, _P]),
     "frlw_coco_workspace_bytes": (_I64, [_I64, _I64, _I64, _I]),
     "frlw_coco_eval": (_I, [_P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _I64, _I, _I, _P, _P, _P, _I64, _P, _P, _P]),
+    "frlw_conv_path_counts": (_I, [C.POINTER(C.c_uint64), _I]),
     "frlw_conv2d_dgrad_parity": (_I, [_I, _I, _I, _I]),
     "frlw_conv_operand_floats": (_I64, [_I, _I, _I]),
     "frlw_conv_weight_layouts": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _P]),

@@ -6,7 +6,8 @@
 //   Y[M = B*Ho*Wo][N = Cout] = A[M][K] * W[K][N],  K = (ky, kx, ci),  A gathered on the fly from an NHWC view.
 //   tstride = 2 turns the gather into that of a transposed (stride-2) convolution: input coordinate
 //   (oy - pad + ky) / 2 when even, zero otherwise -- the data gradient of a stride-2 convolution.
-// (no #includes here: the including file has <hip/hip_runtime.h>, <math.h>, <stdint.h>, <stdlib.h> already)
+// (no #includes here: the including file has <hip/hip_runtime.h>, <math.h>, <stdint.h>, <stdlib.h>, <atomic> and
+// frlw_evd.h already)
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -25,6 +26,14 @@ inline long long dev_knob(const char *name, long long dflt) { const char *e = ge
 constexpr long long dev_knob(const char *, long long dflt) { return dflt; }
 #define FRLW_DEV_LOG(...) do { } while (0)
 #endif
+
+// Which form launch_conv / launch_wgrad_tiles enqueued (frlw_conv_path_counts, FRLW_CONV_PATH_* of frlw_evd.h): host-side
+// relaxed adds, no launch.  ONE array for the library, not one per translation unit that includes this file: the
+// includers' anonymous namespace is left for its definition (a C++17 inline variable, merged by the linker).
+} // namespace
+inline std::atomic<unsigned long long> g_conv_path_counts[FRLW_CONV_PATH_COUNT];
+namespace {
+inline void conv_count(int path) { g_conv_path_counts[path].fetch_add(1ull, std::memory_order_relaxed); }
 
 enum : int { ACT_NONE = 0, ACT_SILU = 1, ACT_SIGMOID = 2 };
 
@@ -1137,6 +1146,7 @@ inline bool launch_conv(ConvArgs &c, float *scratch, long long scratch_floats, h
     const int n_groups = c.group_n ? (c.Npad + c.group_n - 1) / c.group_n : 1;
     const long long x_bytes = (((long long)(nb - 1) * c.x_bs) + ((long long)c.H * c.W - 1) * c.x_cs + c.x_co + (long long)c.Cin * n_groups) * 4;
     if (x_bytes > kMaxViewBytes && nb > 1 && c.M == nb * howo) { // 32-bit buffer offsets: run the batch in two halves
+        conv_count(FRLW_CONV_PATH_HALF_BATCH);
         ConvArgs h = c;
         h.stats = nullptr; // (two launches would write the same slabs: the caller runs its own statistics pass)
         c.stats = nullptr;
@@ -1155,6 +1165,8 @@ inline bool launch_conv(ConvArgs &c, float *scratch, long long scratch_floats, h
     }
     if (x_bytes > kMaxViewBytes || (long long)c.K * c.Npad * 4 > kMaxViewBytes) return false;
     c.x_bytes = (uint32_t)x_bytes;
+    if (c.Cin % 16) conv_count(FRLW_CONV_PATH_GATHERED); // (every tile takes k-tiles of 16: uniform taps need Cin % 16 == 0)
+    if (c.y_rp) conv_count(FRLW_CONV_PATH_PARITY);
     c.w_bytes = (uint32_t)((long long)(c.prec == 1 ? (c.K + 15) / 16 * 16 : c.K) * c.Npad * 4);
     c.splits = 1;
     c.partial = nullptr;
@@ -1181,18 +1193,22 @@ inline bool launch_conv(ConvArgs &c, float *scratch, long long scratch_floats, h
 #endif
     if (c.Npad <= 32) { // small N (prediction convs, the stem's data gradient)
         grant_stats(128);
+        conv_count(FRLW_CONV_PATH_128X32);
         launch_conv_tile<128, 32, 4, 1, 16>(c, dim3((c.M + 127) / 128, 1), s);
     } else if (c.prec == 1 && c.Npad >= 128 && big >= row4_min && c.K >= 512) {
         // bf16 k-steps: the four wavefronts side by side in M, each 32 rows x 128 columns -- a wavefront splits its gathered
         // values (24 VALU instructions per k-step) once for FOUR column tiles; with 2 x 2 the split cost as much issue time as the MFMAs
         grant_stats(128);
+        conv_count(FRLW_CONV_PATH_128X128_4X1);
         launch_conv_tile_p1<128, 128, 4, 1>(c, dim3((c.M + 127) / 128, (c.Npad + 127) / 128), s);
     } else if (big >= big_min && c.Npad >= 128) {
         grant_stats(128);
+        conv_count(FRLW_CONV_PATH_128X128_2X2);
         launch_conv_tile<128, 128, 2, 2, CONV_BK_BIG>(c, dim3((c.M + 127) / 128, (c.Npad + 127) / 128), s);
     } else if (c.Npad >= 128 && (long long)((c.M + 63) / 64) * ((c.Npad + 127) / 128) >= wide_min) {
         // 64 x 128: half the im2col gathers per output of the 64 x 64 tile, still > 4 workgroups per CU
         grant_stats(64);
+        conv_count(FRLW_CONV_PATH_64X128);
         launch_conv_tile<64, 128, 2, 2, 16>(c, dim3((c.M + 63) / 64, (c.Npad + 127) / 128), s);
     } else {
         static const long long w2 = dev_knob("FRLW_CONV_W2", 0ll); // bf16 k-steps, two wavefronts of 32 x 64 (bit 0) / 32 x 128 (bit 1) per workgroup
@@ -1233,6 +1249,7 @@ inline bool launch_conv(ConvArgs &c, float *scratch, long long scratch_floats, h
             (long long)((c.M + 63) / 64) * ((c.Npad + 63) / 64) <= 1024) {
             c.sk_counters = sk_counters;
             if (stats_ok && !c.bias && c.act == ACT_NONE && !c.res) { c.stats = stats_req; c.stats_rows = (c.M + 63) / 64; } // the last arriver has the whole tile
+            conv_count(c.stats ? FRLW_CONV_PATH_SPLIT_INKERNEL_STATS : FRLW_CONV_PATH_SPLIT_INKERNEL);
             hipLaunchKernelGGL((k_conv_mfma_sk<CONV_BK_SMALL>), dim3((c.M + 63) / 64, (c.Npad + 63) / 64, c.splits), dim3(256), 0, s, c);
             return true;
         }
@@ -1244,6 +1261,7 @@ inline bool launch_conv(ConvArgs &c, float *scratch, long long scratch_floats, h
         else
 #endif
         launch_conv_tile<64, 64, 2, 2, CONV_BK_SMALL>(c, dim3((c.M + 63) / 64, (c.Npad + 63) / 64, c.splits), s);
+        conv_count(c.splits == 1 ? FRLW_CONV_PATH_64X64 : vec ? FRLW_CONV_PATH_SPLIT_VEC : FRLW_CONV_PATH_SPLIT_SCALAR);
         if (c.splits > 1) {
             if (vec) hipLaunchKernelGGL(k_splitk_reduce<true>, dim3(conv_grid_1d((long long)c.M * c.Cout / 4)), dim3(256), 0, s, c);
             else hipLaunchKernelGGL(k_splitk_reduce<false>, dim3(conv_grid_1d((long long)c.M * c.Cout)), dim3(256), 0, s, c);

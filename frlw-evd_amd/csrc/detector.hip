@@ -25,6 +25,7 @@
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <atomic>
 #include <utility>
 #include <vector>
 

@@ -24,6 +24,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <atomic>
+
 #include "frlw_evd.h"
 
 namespace {
@@ -491,6 +493,13 @@ inline int npad32(int n) { return (n + 31) / 32 * 32; }
 
 extern "C" {
 
+int frlw_conv_path_counts(uint64_t *counts, int n)
+{
+    if (!counts || n < 1) return FRLW_ERR_ARG;
+    for (int i = 0; i < n && i < FRLW_CONV_PATH_COUNT; ++i) counts[i] = (uint64_t)g_conv_path_counts[i].load(std::memory_order_relaxed);
+    return FRLW_CONV_PATH_COUNT;
+}
+
 int frlw_conv2d_dgrad_parity(int k, int stride, int H, int W)
 {
     return (stride == 2 && k == 3 && !(H & 1) && !(W & 1)) ? 1 : 0;
@@ -654,8 +663,10 @@ int frlw_conv2d_wgrad(const float *x, int B, int H, int W, int Cin, const float 
     a.k = k; a.stride = stride; a.pad = (k - 1) / 2;
     a.R = k * k * Cin; a.M = B * Ho * Wo;
     const long long per = (long long)a.R * Cout;
-    const long long sp = wgrad_splits_for(scratch_floats, per, frlw_conv2d_wgrad_scratch_floats(B, Ho, Wo, Cin, Cout, k));
+    const long long want = frlw_conv2d_wgrad_scratch_floats(B, Ho, Wo, Cin, Cout, k);
+    const long long sp = wgrad_splits_for(scratch_floats, per, want);
     if (sp < 1) return FRLW_ERR_WORKSPACE;
+    if (sp < wgrad_splits_for(want, per, want)) conv_count(FRLW_CONV_PATH_WGRAD_SCRATCH_LIMITED);
     a.splits = (int)sp;
     a.partial = scratch;
     hipStream_t s = (hipStream_t)stream;
@@ -664,6 +675,7 @@ int frlw_conv2d_wgrad(const float *x, int B, int H, int W, int Cin, const float 
     int final_n = a.splits;
     if (a.splits > 64) { // group sums go behind the partial tiles (the scratch query reserves the room)
         const int groups = (a.splits + kWgradGroup - 1) / kWgradGroup;
+        conv_count(FRLW_CONV_PATH_WGRAD_GROUP_SUM);
         float *gs = scratch + (long long)a.splits * per;
         hipLaunchKernelGGL(k_wgrad_group_sum, dim3(conv_grid_1d(per), groups), dim3(256), 0, s, scratch, a.splits, per, gs);
         final_src = gs;

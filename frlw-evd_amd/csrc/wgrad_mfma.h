@@ -227,6 +227,8 @@ inline bool launch_wgrad_tiles(WgradArgs &a, hipStream_t s) // a.splits and a.pa
     if (xb > kMaxViewBytes || zb > kMaxViewBytes) return false; // 32-bit buffer offsets
     a.x_bytes = (uint32_t)xb;
     a.dz_bytes = (uint32_t)zb;
+    conv_count(wgrad_wide(a.R, a.Cout) ? FRLW_CONV_PATH_WGRAD_128X128 : a.R > 64 && a.Cout <= 32 ? FRLW_CONV_PATH_WGRAD_128X32
+               : a.R > 64 ? FRLW_CONV_PATH_WGRAD_128X64 : FRLW_CONV_PATH_WGRAD_64X64);
     if (a.prec == 1) {
         if (wgrad_wide(a.R, a.Cout))
             hipLaunchKernelGGL((k_wgrad_mfma<128, 128, WGRAD_NBUF, 2, 2, 1>), dim3((a.R + 127) / 128, (a.Cout + 127) / 128, a.splits), dim3(256), 0, s, a);

@@ -535,6 +535,39 @@ typedef struct frlw_weight_layout_item {
     int32_t split, reserved2; /* operands of two BaseConvs stacked along the output channels (frlw_baseconv_fuse_t::split) */
 } frlw_weight_layout_item_t;
 int frlw_conv_weight_layouts_batch(const frlw_weight_layout_item_t *items, int n, int64_t total, frlw_stream_t stream);
+/* Which form every convolution and weight gradient of this process took (frlw_conv2d_fwd / _dgrad / _wgrad, the train-mode
+ * BaseConv calls and the convolutions of frlw_det_run alike), counted per process since it loaded the library -- diagnostics
+ * and tests that must know which kernel a shape reaches.  The counts are host-side: they count ENQUEUES, so the replays of a
+ * captured hipGraph add nothing.  Each convolution launch counts one of 128X32 .. SPLIT_SCALAR (its tile, or for the 64 x 64
+ * tile how the contraction is reduced: whole, split + k_splitk_reduce<vector | scalar>, split reduced inside the kernel with
+ * or without the BatchNorm statistics of the train forward) and may count GATHERED (Cin % 16 != 0: taps gathered per k-tile)
+ * and PARITY (one parity class of a stride-2 data gradient); HALF_BATCH counts each split of a batch whose view exceeds the
+ * 32-bit buffer offsets.  Each weight gradient counts one WGRAD tile, and GROUP_SUM / SCRATCH_LIMITED when it sums its
+ * partial tiles in groups / takes fewer splits than frlw_conv2d_wgrad_scratch_floats asked for.
+ * frlw_conv_path_counts copies the first min(n, FRLW_CONV_PATH_COUNT) counters to `counts` (HOST memory) and returns
+ * FRLW_CONV_PATH_COUNT; NULL or n < 1: FRLW_ERR_ARG. */
+enum {
+    FRLW_CONV_PATH_128X32 = 0,
+    FRLW_CONV_PATH_128X128_4X1,          /* bf16x3 only */
+    FRLW_CONV_PATH_128X128_2X2,
+    FRLW_CONV_PATH_64X128,
+    FRLW_CONV_PATH_64X64,                /* whole contraction */
+    FRLW_CONV_PATH_SPLIT_VEC,            /* 64 x 64, split-K + k_splitk_reduce<true> */
+    FRLW_CONV_PATH_SPLIT_SCALAR,         /* 64 x 64, split-K + k_splitk_reduce<false> */
+    FRLW_CONV_PATH_SPLIT_INKERNEL,       /* k_conv_mfma_sk */
+    FRLW_CONV_PATH_SPLIT_INKERNEL_STATS, /* k_conv_mfma_sk leaving the BatchNorm statistics too */
+    FRLW_CONV_PATH_GATHERED,
+    FRLW_CONV_PATH_HALF_BATCH,
+    FRLW_CONV_PATH_PARITY,
+    FRLW_CONV_PATH_WGRAD_128X128,
+    FRLW_CONV_PATH_WGRAD_128X32,
+    FRLW_CONV_PATH_WGRAD_128X64,
+    FRLW_CONV_PATH_WGRAD_64X64,
+    FRLW_CONV_PATH_WGRAD_GROUP_SUM,
+    FRLW_CONV_PATH_WGRAD_SCRATCH_LIMITED,
+    FRLW_CONV_PATH_COUNT
+};
+int frlw_conv_path_counts(uint64_t *counts, int n);
 /* z (B, Ho, Wo, Cout) = conv2d(x (B, H, W, Cin), w), padding (k - 1) / 2, stride 1 or 2.  scratch: optional split-K
  * partial sums (scratch_floats floats; NULL = never split). */
 int frlw_conv2d_fwd(const float *x, int B, int H, int W, int Cin, const float *w_fwd, int Cout, int k, int stride, float *z,
