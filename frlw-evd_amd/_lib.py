@@ -25,6 +25,9 @@ CONV_PATHS = ("128x32", "128x128_4x1", "128x128_2x2", "64x128", "64x64", "split_
               "split_inkernel_stats", "gathered", "half_batch", "parity", "wgrad_128x128", "wgrad_128x32", "wgrad_128x64",
               "wgrad_64x64", "wgrad_group_sum", "wgrad_scratch_limited")
 
+# the FRLW_BN_PATH_* counters of frlw_bn_path_counts, in the header's enum order (lower case, prefix dropped)
+BN_PATHS = ("stats_pass", "stats_epilogue", "stats_split_inkernel", "fwd", "fwd_fused", "bwd", "bwd_pair")
+
 LAYOUT_XYTP_F64 = 0
 LAYOUT_DAT8 = 1
 TAF_U8_FLIP_K = 1
@@ -146,6 +149,7 @@ SYMBOLS = {
     "frlw_conv2d_dgrad": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _I64, _I, _P]),
     "frlw_conv2d_wgrad_scratch_floats": (_I64, [_I, _I, _I, _I, _I, _I]),
     "frlw_conv2d_wgrad": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _I64, _I, _P]),
+    "frlw_bn_path_counts": (_I, [C.POINTER(C.c_uint64), _I]),
     "frlw_bn_scratch_doubles": (_I64, [_I64, _I]),
     "frlw_bn_stats": (_I, [_P, _I64, _I, C.c_float, _P, _P, _P, _P, _P]),
     "frlw_bn_silu_fwd": (_I, [_P, _I64, _I, _P, _P, _P, _P, _P, _P]),

@@ -102,6 +102,20 @@ constexpr int kSplitBK = 16; // granularity the split-K heuristics count k-tiles
 #define CONV_F32_PIPE 1 // 0: the float32-MFMA loop without the pipelined iteration seam (A/B in tools/conv_lab.hip)
 #endif
 
+// BatchNorm statistics in the train forward's epilogues (ConvArgs::stats).  Sums of squares of raw float32 values lose what
+// little is left of the variance when a channel's mean dominates its spread (every square is rounded to 2^-24 of mean^2).
+// So a wavefront sums, in float32, the SHIFTED values d = v - k and d^2 over its rows inside M, k = the column's value in the
+// wavefront's first row (within a few standard deviations of the mean: no cancellation in d), and the float64 slab gets the
+// plain moments back: sum v = n k + sum d, sum v^2 = n k^2 + 2 k sum d + sum d^2 over the n rows of the wavefront inside M.
+// k_bn_stats_final's mean square minus squared mean then cancels in float64 (2^-53 relative, times (mean / std)^2).
+// st = {sum d, sum d^2, k, -} over n rows.
+__device__ __forceinline__ void conv_stats_unshift(const float4 st, int n_rows, double &s, double &q)
+{
+    const double n = (double)n_rows, k = st.z;
+    s += n * k + (double)st.x;
+    q += (n * k) * k + 2.0 * k * (double)st.x + (double)st.y;
+}
+
 __device__ __forceinline__ float act_apply(float v, int act)
 {
     // hardware exponential and reciprocal (~2 ulp): the epilogue runs with no MFMA left to hide it, and the detector's
@@ -651,7 +665,10 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a)
             const int n = n0 + wc * 32 + ec;
             float4 bias4 = make_float4(0.f, 0.f, 0.f, 0.f);
             if (a.bias && n < a.Cout) bias4 = *(const float4 *)(a.bias + n);
-            float st_s[4] = {0.0f, 0.0f, 0.0f, 0.0f}, st_q[4] = {0.0f, 0.0f, 0.0f, 0.0f}; // a.stats: column sums of this lane's four rows
+            // a.stats: column sums of this lane's four rows, shifted by the column's value in the wavefront's first row -- kept in
+            // LDS (st_k: [wavefront][32 columns] behind the staging area below), not in registers, which this loop has none left of
+            float st_s[4] = {0.0f, 0.0f, 0.0f, 0.0f}, st_q[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            float *const st_k = smem + 4 * 4 * 32 + wv * 32;
 #pragma unroll
             for (int tp = 0; tp < 4 / SK_ROWS; ++tp) { // two of the thread's four rows at a time: 16 loads in flight (the registers of 32 would cost the main loop a wavefront per SIMD)
                 f32x4 part[SK_ROWS][8];
@@ -673,9 +690,18 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a)
 #pragma unroll
                     for (int z = 0; z < 8; ++z)
                         if (z < a.splits) { v[0] += part[tt][z][0]; v[1] += part[tt][z][1]; v[2] += part[tt][z][2]; v[3] += part[tt][z][3]; }
-                    if (a.stats && m < a.M) { // (workgroup-uniform pointer; train forward: no bias, no activation -- v is z)
+                    if (a.stats) { // (workgroup-uniform pointer; train forward: no bias, no activation -- v is z)
+                        if (tp == 0 && tt == 0) { // row m0 + wr * 32 (lanes 0..7 hold it; past M: every row of the wavefront is left out)
+                            if (lane < 8) *(float4 *)(st_k + ec) = make_float4(v[0], v[1], v[2], v[3]);
+                            __syncthreads(); // (the operand tiles are free: every wavefront is past the barrier above)
+                        }
+                        const f32x4 k4 = *(const f32x4 *)(st_k + ec);
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) { st_s[e] += v[e]; st_q[e] += v[e] * v[e]; }
+                        for (int e = 0; e < 4; ++e) {
+                            const float d = m < a.M ? v[e] - k4[e] : 0.0f;
+                            st_s[e] += d;
+                            st_q[e] += d * d;
+                        }
                     }
                     if (m < a.M && n < a.Cout) {
                         const float bb[4] = {bias4.x, bias4.y, bias4.z, bias4.w};
@@ -696,24 +722,29 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a)
                 }
             }
             if (a.stats) {
-                // BatchNorm statistics of the train step from the finished tile, like the unsplit epilogue below: float32 inside a
-                // wavefront's 32 rows (four rows per lane, then the eight lanes that share a column quad), float64 across the two
-                // wavefronts of a column half and in the stored slab (one slab per 64-row tile) -- k_bn_stats_partial goes away
-                // for the layers that split their contraction
+                // BatchNorm statistics of the train step from the finished tile, like the unsplit epilogue below: shifted float32
+                // sums inside a wavefront's 32 rows (four rows per lane, then the eight lanes that share a column quad), float64
+                // across the two wavefronts of a column half and in the stored slab (one slab per 64-row tile) -- k_bn_stats_partial
+                // goes away for the layers that split their contraction
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
 #pragma unroll
                     for (int off = 8; off <= 32; off <<= 1) { st_s[e] += __shfl_xor(st_s[e], off); st_q[e] += __shfl_xor(st_q[e], off); }
-                float2 *stg = (float2 *)smem; // [wavefront][32 columns] (the operand tiles are free: every wavefront is past the barrier above)
+                float4 *stg = (float4 *)smem; // [wavefront][32 columns]
                 if (lane < 8) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) stg[wv * 32 + ec + e] = make_float2(st_s[e], st_q[e]);
+                    for (int e = 0; e < 4; ++e) stg[wv * 32 + ec + e] = make_float4(st_s[e], st_q[e], st_k[ec + e], 0.0f);
                 }
                 __syncthreads();
                 if (wr == 0 && lane < 32) {
-                    const float2 v0 = stg[(0 * WCOLS + wc) * 32 + lane], v1 = stg[(1 * WCOLS + wc) * 32 + lane];
+                    double ds = 0.0, dq = 0.0;
+#pragma unroll
+                    for (int w = 0; w < 2; ++w) {
+                        const int rows = a.M - (m0 + w * 32); // (rows of the wavefront inside M: <= 0 or beyond 32 at the edges)
+                        conv_stats_unshift(stg[(w * WCOLS + wc) * 32 + lane], rows <= 0 ? 0 : (rows < 32 ? rows : 32), ds, dq);
+                    }
                     const int nn = n0 + wc * 32 + lane;
-                    if (nn < a.Cout) *(double2 *)(a.stats + ((long long)blockIdx.x * a.Cout + nn) * 2) = make_double2((double)v0.x + (double)v1.x, (double)v0.y + (double)v1.y);
+                    if (nn < a.Cout) *(double2 *)(a.stats + ((long long)blockIdx.x * a.Cout + nn) * 2) = make_double2(ds, dq);
                 }
             }
             return;
@@ -728,19 +759,42 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a)
         const int er = lane >> 3, ec = (lane & 7) * 4; // this lane's rows er, er + 8, er + 16, er + 24; columns ec..ec+3
         if (a.stats) { // (workgroup-uniform)
             // BatchNorm statistics of the train step straight from the accumulators: the column sums of the workgroup's BM rows
-            // (rows past M are zero) -- float32 inside a wavefront's 32 * TM rows, float64 across the wavefronts and in the
-            // stored slab -- so the separate pass over z (k_bn_stats_partial) goes away
-            float2 *stg = (float2 *)smem; // [wavefront][TN * 32 columns]: the operand tiles are free after the last barrier
+            // -- shifted float32 sums inside a wavefront's 32 * TM rows (conv_stats_unshift), float64 across the wavefronts and
+            // in the stored slab -- so the separate pass over z (k_bn_stats_partial) goes away.  The wavefront that holds row
+            // M - 1 (rows past M are zero in the accumulators) adds exact float64 squares instead: a shift would need a mask per
+            // value, and the masks cost the kernel a wavefront per SIMD.
+            float4 *stg = (float4 *)smem; // [wavefront][TN * 32 columns]: the operand tiles are free after the last barrier
+            const bool whole = a.M - (m0 + wr * TM * 32) >= 32 * TM; // (wavefront-uniform) every row of the wavefront inside M
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
-                float cs = 0.0f, cq = 0.0f;
+                if (whole) {
+                    const float K = __shfl(acc[0][j][0], lane & 31); // the column's value in the wavefront's first row
+                    float cs = 0.0f, cq = 0.0f;
 #pragma unroll
-                for (int i = 0; i < TM; ++i)
+                    for (int i = 0; i < TM; ++i)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) { cs += acc[i][j][r]; cq += acc[i][j][r] * acc[i][j][r]; }
-                cs += __shfl_xor(cs, 32);
-                cq += __shfl_xor(cq, 32);
-                if (lane < 32) stg[(wv * TN + j) * 32 + lane] = make_float2(cs, cq);
+                        for (int r = 0; r < 16; ++r) {
+                            const float d = acc[i][j][r] - K;
+                            cs += d;
+                            cq += d * d;
+                        }
+                    cs += __shfl_xor(cs, 32);
+                    cq += __shfl_xor(cq, 32);
+                    if (lane < 32) stg[(wv * TN + j) * 32 + lane] = make_float4(cs, cq, K, 0.0f);
+                } else {
+                    double ds = 0.0, dq = 0.0;
+#pragma unroll
+                    for (int i = 0; i < TM; ++i)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const double v = (double)acc[i][j][r];
+                            ds += v;
+                            dq += v * v;
+                        }
+                    ds += __shfl_xor(ds, 32);
+                    dq += __shfl_xor(dq, 32);
+                    if (lane < 32) ((double2 *)stg)[(wv * TN + j) * 32 + lane] = make_double2(ds, dq);
+                }
             }
             __syncthreads();
             if (wr == 0 && lane < 32) {
@@ -749,9 +803,14 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a)
                     double ds = 0.0, dq = 0.0;
 #pragma unroll
                     for (int w = 0; w < WROWS; ++w) { // wavefront (w, wc) = w * WCOLS + wc
-                        const float2 v = stg[((w * WCOLS + wc) * TN + j) * 32 + lane];
-                        ds += (double)v.x;
-                        dq += (double)v.y;
+                        const int at = ((w * WCOLS + wc) * TN + j) * 32 + lane;
+                        if (a.M - (m0 + w * TM * 32) >= 32 * TM) {
+                            conv_stats_unshift(stg[at], 32 * TM, ds, dq);
+                        } else {
+                            const double2 p = ((const double2 *)stg)[at];
+                            ds += p.x;
+                            dq += p.y;
+                        }
                     }
                     const int n = n0 + wc * TN * 32 + 32 * j + lane;
                     if (n < a.Cout) *(double2 *)(a.stats + ((long long)blockIdx.x * a.Cout + n) * 2) = make_double2(ds, dq);

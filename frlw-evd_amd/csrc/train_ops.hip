@@ -10,7 +10,7 @@
 //   frlw_conv2d_wgrad          dw = x^T * dz                     k_wgrad_mfma: M = k*k*Cin, N = Cout, contraction over
 //                              the B*Ho*Wo output pixels split over blockIdx.z, deterministic two-stage reduction
 //                              straight into torch's (Cout, Cin, k, k) layout
-//   frlw_bn_stats              per-channel mean / biased variance (float64 accumulation, two-stage, deterministic)
+//   frlw_bn_stats              per-channel mean / biased variance (float64 sums, two-stage, deterministic)
 //   frlw_bn_silu_fwd           y = silu(gamma * (z - mean) * invstd + beta)
 //   frlw_bn_silu_bwd           dz, dgamma, dbeta from dy and z (u recomputed, nothing but z saved)
 //
@@ -241,10 +241,11 @@ __host__ __device__ inline int bn_rows_per_wg(long long M)
     return (int)r;
 }
 
-// F32_GROUPS: the four rows in flight are added in float32 before they enter the float64 sums (one conversion and one f64 add
-// per four rows instead of four each; f64 runs at half rate on this part).  Used for the backward sums only: the statistics
-// pass keeps every term in float64 (sum of squares minus squared mean cancels).
-template <bool F32_GROUPS = false, typename F>
+// f writes the eight terms of a row and float4 column into T[8].  F32_GROUPS: the four rows in flight are added in float32
+// before they enter the float64 sums (one conversion and one f64 add per four rows instead of four each; f64 runs at half
+// rate on this part).  Used for the backward sums only: the statistics pass squares in float64 (T = double: the square of a
+// float32 is exact there) and adds in float64, because its sum of squares minus squared mean cancels.
+template <typename T = float, bool F32_GROUPS = false, typename F>
 __device__ __forceinline__ void bn_reduce_rows(long long M, int C, double *partial, F f)
 {
     __shared__ double red[256][8];
@@ -264,14 +265,14 @@ __device__ __forceinline__ void bn_reduce_rows(long long M, int C, double *parti
         if (rl < lanes) {
             long long r = row0 + rl;
             for (; r + 3ll * lanes < row1; r += 4ll * lanes) { // four independent rows in flight
-                float a0[8], a1[8], a2[8], a3[8];
+                T a0[8], a1[8], a2[8], a3[8];
                 f(r, c, a0); f(r + lanes, c, a1); f(r + 2ll * lanes, c, a2); f(r + 3ll * lanes, c, a3);
 #pragma unroll
                 for (int i = 0; i < 8; ++i)
                     acc[i] += F32_GROUPS ? (double)((a0[i] + a1[i]) + (a2[i] + a3[i])) : ((double)a0[i] + (double)a1[i]) + ((double)a2[i] + (double)a3[i]);
             }
             for (; r < row1; r += lanes) {
-                float a0[8];
+                T a0[8];
                 f(r, c, a0);
 #pragma unroll
                 for (int i = 0; i < 8; ++i) acc[i] += (double)a0[i];
@@ -292,13 +293,13 @@ __device__ __forceinline__ void bn_reduce_rows(long long M, int C, double *parti
     }
 }
 
-// partial[wg][c] = {sum, sum of squares} in float64
+// partial[wg][c] = {sum, sum of squares} in float64 (every term exact)
 __global__ __launch_bounds__(256) void k_bn_stats_partial(const float *z, long long M, int C, double *partial)
 {
-    bn_reduce_rows(M, C, partial, [=](long long r, int c, float (&o)[8]) {
+    bn_reduce_rows<double>(M, C, partial, [=](long long r, int c, double (&o)[8]) {
         const float4 v = *(const float4 *)(z + r * C + c);
         o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
-        o[4] = v.x * v.x; o[5] = v.y * v.y; o[6] = v.z * v.z; o[7] = v.w * v.w;
+        o[4] = o[0] * o[0]; o[5] = o[1] * o[1]; o[6] = o[2] * o[2]; o[7] = o[3] * o[3];
     });
 }
 
@@ -337,6 +338,10 @@ __device__ __forceinline__ void bn_sum_partials(const double *partial, int n_wg,
 
 // mean, biased variance, invstd = 1 / sqrt(var + eps) in float32 (what BatchNorm2d normalises with)
 // (+ the running statistics of nn.BatchNorm2d when given: momentum update with the unbiased variance)
+// The partials are plain float64 {sum, sum of squares} from every producer (k_bn_stats_partial; the convolution epilogues form
+// theirs from shifted float32 sums, conv_mfma.h conv_stats_unshift), so the variance E v^2 - mu^2 cancels in float64: a
+// channel whose mean is 1000 standard deviations loses 2^-53 * 1e6 of its variance.  M = 1: the variance is 0, and the
+// running variance takes it as the unbiased one too (nn.BatchNorm2d refuses such a batch in training).
 // (pair: two BaseConvs stacked along the channels -- channels >= split update the second block's running statistics)
 struct RunStats2 { float *run_mean2, *run_var2; long long *tracked2; int split; };
 __global__ __launch_bounds__(256) void k_bn_stats_final(const double *partial, int n_wg, int C, long long M, float eps,
@@ -430,7 +435,7 @@ __global__ __launch_bounds__(256) void k_bn_silu_bwd_partial(const Rows2 dyr, co
                                                              const Aff2 ab, const float *mean,
                                                              const float *invstd, double *partial)
 {
-    bn_reduce_rows<true>(M, C, partial, [=](long long r, int c, float (&o)[8]) {
+    bn_reduce_rows<float, true>(M, C, partial, [=](long long r, int c, float (&o)[8]) {
         const float *gamma = ab.g, *beta = ab.b;
         if (PAIR) aff_of(ab, c, gamma, beta);
         const float4 zv = *(const float4 *)(z + r * C + c), gv = *(const float4 *)(PAIR ? row_of(dyr, r, c) : dyr.p + r * dyr.rs + c);
@@ -489,6 +494,10 @@ __global__ void k_bn_silu_bwd_apply(const Rows2 dyr, const float *z, long long n
 
 inline int npad32(int n) { return (n + 31) / 32 * 32; }
 
+// Which BatchNorm + SiLU form was enqueued (frlw_bn_path_counts, FRLW_BN_PATH_* of frlw_evd.h): host-side relaxed adds, no launch
+std::atomic<unsigned long long> g_bn_path_counts[FRLW_BN_PATH_COUNT];
+inline void bn_count(int path) { g_bn_path_counts[path].fetch_add(1ull, std::memory_order_relaxed); }
+
 } // namespace
 
 extern "C" {
@@ -498,6 +507,13 @@ int frlw_conv_path_counts(uint64_t *counts, int n)
     if (!counts || n < 1) return FRLW_ERR_ARG;
     for (int i = 0; i < n && i < FRLW_CONV_PATH_COUNT; ++i) counts[i] = (uint64_t)g_conv_path_counts[i].load(std::memory_order_relaxed);
     return FRLW_CONV_PATH_COUNT;
+}
+
+int frlw_bn_path_counts(uint64_t *counts, int n)
+{
+    if (!counts || n < 1) return FRLW_ERR_ARG;
+    for (int i = 0; i < n && i < FRLW_BN_PATH_COUNT; ++i) counts[i] = (uint64_t)g_bn_path_counts[i].load(std::memory_order_relaxed);
+    return FRLW_BN_PATH_COUNT;
 }
 
 int frlw_conv2d_dgrad_parity(int k, int stride, int H, int W)
@@ -551,7 +567,7 @@ int frlw_conv_weight_layouts_batch(const frlw_weight_layout_item_t *items, int n
 static int conv_common(const float *x, int B, int H, int W, int Cin, const float *w_gemm, int Cout, int k, int stride,
                        int tstride, int Ho, int Wo, float *y, float *scratch, int64_t scratch_floats, int precision, hipStream_t s,
                        double *stats = nullptr, int *stats_rows = nullptr, int *sk_counters = nullptr, const float *res = nullptr,
-                       long long res_rs = 0)
+                       long long res_rs = 0, bool *stats_split = nullptr)
 {
     if (precision != 0 && precision != 1) return FRLW_ERR_ARG;
     (void)hipGetLastError(); // other libraries in the process (torch's BLAS look-ups) leave stale errors behind
@@ -568,6 +584,7 @@ static int conv_common(const float *x, int B, int H, int W, int Cin, const float
     c.stats = stats;
     if (!launch_conv(c, scratch, scratch ? scratch_floats : 0, s, sk_counters)) return FRLW_ERR_UNSUPPORTED;
     if (stats_rows) *stats_rows = c.stats ? c.stats_rows : 0;
+    if (stats_split) *stats_split = c.stats && c.splits > 1; // the in-kernel split-K epilogue wrote them, else the unsplit one
     if (hipGetLastError() != hipSuccess) return FRLW_ERR_HIP;
     return FRLW_OK;
 }
@@ -712,8 +729,12 @@ static int bn_stats_impl(const float *z, int64_t M, int C, float eps, float *mea
     if (!z || !mean || !var || !invstd || !scratch || M < 1 || C < 4 || (C & 3)) return FRLW_ERR_ARG;
     int n_wg = (int)((M + bn_rows_per_wg(M) - 1) / bn_rows_per_wg(M));
     hipStream_t s = (hipStream_t)stream;
-    if (have_partials > 0) n_wg = have_partials; // the convolution's epilogue has written `have_partials` slabs into scratch
-    else hipLaunchKernelGGL(k_bn_stats_partial, dim3(n_wg), dim3(256), 0, s, z, (long long)M, C, scratch);
+    if (have_partials > 0) { // the convolution's epilogue has written `have_partials` slabs into scratch
+        n_wg = have_partials;
+    } else {
+        bn_count(FRLW_BN_PATH_STATS_PASS);
+        hipLaunchKernelGGL(k_bn_stats_partial, dim3(n_wg), dim3(256), 0, s, z, (long long)M, C, scratch);
+    }
     hipLaunchKernelGGL(k_bn_stats_final, dim3((C + kFinCh - 1) / kFinCh), dim3(256), 0, s, scratch, n_wg, C, (long long)M, eps, mean,
                        var, invstd, run_mean, run_var, momentum, batches_tracked, pr);
     TRY_HIP(hipGetLastError());
@@ -737,6 +758,7 @@ static int bn_silu_fwd_impl(const float *z, int64_t M, int C, const float *gamma
     if (split > 0 && (y2_rs < C - c1 || (y2_rs & 3) || ((uintptr_t)y2 & 15))) return FRLW_ERR_ARG;
     const long long n4 = (long long)M * C / 4;
     const Aff2 ab = {gamma, beta, gamma2, beta2, split > 0 ? split : 0};
+    bn_count(res || y_rs != C || split > 0 ? FRLW_BN_PATH_FWD_FUSED : FRLW_BN_PATH_FWD);
     if (res || y_rs != C || split > 0)
         hipLaunchKernelGGL(k_bn_silu_fwd<true>, dim3(conv_grid_1d(n4)), dim3(256), 0, (hipStream_t)stream, z, n4, C, ab, mean,
                            invstd, y, (long long)y_rs, res, (long long)res_rs, y2, (long long)y2_rs);
@@ -773,6 +795,7 @@ static int bn_silu_bwd_impl(const float *dy, int64_t dy_row_stride, const float 
     const Aff2 ab = {gamma, beta, gamma2, beta2, split > 0 ? split : 0};
     const Rows2 dyr = {dy, dy_rs, dy2, dy2_rs, split > 0 ? split : 0};
     const long long n4 = (long long)M * C / 4;
+    bn_count(split > 0 ? FRLW_BN_PATH_BWD_PAIR : FRLW_BN_PATH_BWD);
     if (split > 0) {
         hipLaunchKernelGGL(k_bn_silu_bwd_partial<true>, dim3(n_wg), dim3(256), 0, s, dyr, z, (long long)M, C, ab, mean, invstd, scratch);
         hipLaunchKernelGGL(k_bn_silu_bwd_final, dim3((C + kFinCh - 1) / kFinCh), dim3(256), 0, s, scratch, n_wg, C, (long long)M, dgamma, dbeta, sums);
@@ -863,8 +886,10 @@ int frlw_baseconv_train_fwd(const float *x, const float *w, const float *gamma, 
     } else if ((rc = weight_layouts_impl(w, w2, split, Cout, Cin, k, 0, t.w_fwd, nullptr, precision, stream)) != FRLW_OK) return rc;
     if (stride != 1 && stride != 2) return FRLW_ERR_UNSUPPORTED;
     int stat_rows = 0; // > 0: the convolution's epilogue left the column sums of its output slabs in t.red
+    bool stat_split = false;
     if ((rc = conv_common(x, B, H, W, Cin, w_fwd, Cout, k, stride, 0, Ho, Wo, z, t.splitk, t.splitk_floats, precision, (hipStream_t)stream,
-                          t.red, &stat_rows, splitk_counters)) != FRLW_OK) return rc;
+                          t.red, &stat_rows, splitk_counters, nullptr, 0, &stat_split)) != FRLW_OK) return rc;
+    if (stat_rows > 0) bn_count(stat_split ? FRLW_BN_PATH_STATS_SPLIT_INKERNEL : FRLW_BN_PATH_STATS_EPILOGUE);
     RunStats2 pr = {nullptr, nullptr, nullptr, 0};
     if (split > 0 && running_mean) {
         if (!fuse->running_mean2 || !fuse->running_var2) return FRLW_ERR_ARG;

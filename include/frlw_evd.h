@@ -582,7 +582,27 @@ int frlw_conv2d_dgrad(const float *dz, int B, int Ho, int Wo, int Cout, const fl
 int64_t frlw_conv2d_wgrad_scratch_floats(int B, int Ho, int Wo, int Cin, int Cout, int k);
 int frlw_conv2d_wgrad(const float *x, int B, int H, int W, int Cin, const float *dz, int Ho, int Wo, int Cout, int k,
                       int stride, float *dw, float *scratch, int64_t scratch_floats, int precision, frlw_stream_t stream);
-/* Per-channel batch statistics of z viewed as (M, C): mean, biased variance, invstd = 1 / sqrt(var + eps).
+/* Which BatchNorm + SiLU form of the train step was enqueued, counted like frlw_conv_path_counts (host-side, ENQUEUES: a
+ * captured hipGraph's replays add nothing).  One of STATS_* per statistics computation, by where the per-channel sums come
+ * from: PASS = a pass over z of its own (frlw_bn_stats, or a train forward whose convolution left no sums), EPILOGUE = the
+ * unsplit convolution's epilogue, SPLIT_INKERNEL = the last arriver of an in-kernel split-K convolution.  FWD / FWD_FUSED: one
+ * normalise + SiLU pass, dense or with a residual, a row stride or a stacked pair.  BWD / BWD_PAIR: one backward (partial
+ * sums, final, apply), one block or a stacked pair.  frlw_bn_path_counts copies the first min(n, FRLW_BN_PATH_COUNT) counters
+ * to `counts` (HOST memory) and returns FRLW_BN_PATH_COUNT; NULL or n < 1: FRLW_ERR_ARG. */
+enum {
+    FRLW_BN_PATH_STATS_PASS = 0,
+    FRLW_BN_PATH_STATS_EPILOGUE,
+    FRLW_BN_PATH_STATS_SPLIT_INKERNEL,
+    FRLW_BN_PATH_FWD,
+    FRLW_BN_PATH_FWD_FUSED,
+    FRLW_BN_PATH_BWD,
+    FRLW_BN_PATH_BWD_PAIR,
+    FRLW_BN_PATH_COUNT
+};
+int frlw_bn_path_counts(uint64_t *counts, int n);
+/* Per-channel batch statistics of z viewed as (M, C): mean, biased variance, invstd = 1 / sqrt(var + eps), accumulated in
+ * float64 (the variance keeps float32 accuracy for any ratio of mean to spread).  M = 1: var = 0 (and a train forward's
+ * running variance is updated with 0 as the unbiased variance; nn.BatchNorm2d refuses M = 1 in training).
  * scratch: frlw_bn_scratch_doubles(M, C) doubles. */
 int64_t frlw_bn_scratch_doubles(int64_t M, int C);
 int frlw_bn_stats(const float *z, int64_t M, int C, float eps, float *mean, float *var, float *invstd, double *scratch,

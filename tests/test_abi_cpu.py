@@ -156,3 +156,29 @@ def test_conv_path_counters_match_the_header_and_start_at_zero():
     assert p.returncode == 0, p.stderr[-3000:]
     n = len(_lib.CONV_PATHS)
     assert p.stdout.split("\n")[-2] == f"{n} {[0] * n + [7, 7]} {n} [0, 9]"
+
+
+def test_bn_path_counters_match_the_header_and_start_at_zero():
+    """frlw_bn_path_counts: the enum of include/frlw_evd.h and _lib.BN_PATHS name the same counters in the same order; NULL /
+    n < 1 are refused; a fresh process (nothing launched) reads all zeros, and a short buffer gets a prefix."""
+    import subprocess
+    import sys
+    text = open(os.path.join(ROOT, "include", "frlw_evd.h")).read()
+    body = re.search(r"enum \{\s*(FRLW_BN_PATH_STATS_PASS = 0,.*?)\};", text, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    names = [n.strip().split("=")[0].strip() for n in body.split(",") if n.strip()]
+    assert names[-1] == "FRLW_BN_PATH_COUNT"
+    assert [n[len("FRLW_BN_PATH_"):].lower() for n in names[:-1]] == list(_lib.BN_PATHS)
+    import ctypes as C
+    lib = _lib.load()
+    assert lib.frlw_bn_path_counts(None, 4) == _lib.FRLW_ERR_ARG
+    buf = (C.c_uint64 * 1)()
+    assert lib.frlw_bn_path_counts(buf, 0) == _lib.FRLW_ERR_ARG
+    code = ("import ctypes as C, sys; sys.path.insert(0, sys.argv[1]); from frlw_evd_amd import _lib; lib = _lib.load(); "
+            "n = len(_lib.BN_PATHS); c = (C.c_uint64 * (n + 2))(*([7] * (n + 2))); "
+            "r = lib.frlw_bn_path_counts(c, n + 2); s = (C.c_uint64 * 2)(9, 9); r2 = lib.frlw_bn_path_counts(s, 1); "
+            "print(r, list(c), r2, list(s))")
+    p = subprocess.run([sys.executable, "-c", code, ROOT], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    n = len(_lib.BN_PATHS)
+    assert p.stdout.split("\n")[-2] == f"{n} {[0] * n + [7, 7]} {n} [0, 9]"

@@ -393,6 +393,12 @@ def test_baseconv_train_forms(case, mode):
         assert forms_moved(before) == bfs, (pname, "backward", forms_moved(before))
         assert int(cnt.abs().sum()) == 0, "arrival counters not reset"
         assert torch.isfinite(dz).all()
+        # BatchNorm + SiLU per channel against float64 on the z the forward returned: statistics (var relative to itself), y, and
+        # the backward's dz, dgamma, dbeta (bounds: test_bn_silu_forms_gpu.py)
+        import test_bn_silu_forms_gpu as bnf
+        bn_ref = bnf.reference(z.reshape(-1, Cout), gamma, beta, dy.reshape(-1, Cout))
+        bnf.assert_ok(bnf.judge(bn_ref, dict(mean=mean, var=var, invstd=invstd, y=y.reshape(-1, Cout), dz=dz.reshape(-1, Cout), dgamma=dgamma,
+                                         dbeta=dbeta)), f"{name} {pname} BatchNorm + SiLU")
         # the data and weight gradients of the dz the BatchNorm backward produced: (b) in both data modes
         judge(dx, dgrad_ref(dz, w, s, H, W), dgrad_ref(dz.abs(), w.abs(), s, H, W), "randn", prec, f"{name} {pname} dx")
         judge(dw, wgrad_ref(x, dz, w.shape, s), wgrad_ref(x.abs(), dz.abs(), w.shape, s), "randn", prec, f"{name} {pname} dw")
