@@ -266,6 +266,37 @@ struct FastEv {
 // time field is replaced by the caller with the event's position in its sequence (the consumer wants the LAST writer).
 // SAE == 2 (Event Count Image, generate_eventcountimage.py:19-41): the Event Volume decode -- x >= W aliases into the next row,
 // a flat pixel outside the frame is an error -- without any time bound (the host passes t0 = -1: every event is kept).
+// The flat index x + W * y of generate_taf.py:23: x >= W aliases into the next row.  false: the flat pixel lies outside the frame.
+__device__ __forceinline__ bool fast_alias(const FastGeom &G, int &x, int &y)
+{
+    if (x >= G.W || y >= G.H_full) {
+        const long long flat = (long long)x + (long long)G.W * y;
+        if (flat >= (long long)G.H_full * G.W) return false;
+        y = (int)(flat / G.W);
+        x = (int)(flat - (long long)y * G.W);
+    }
+    return true;
+}
+
+// The SIMPLE TAF fields of an in-frame event at time t: window, tile (bin) and record word.  false: t is outside
+// [t0, t0 + span] (ST_SPAN); the fields are computed either way, so a caller can select instead of branching (kf_scatter_cm).
+// (y >> thl < tiles_y and tiles_x are both at most kMaxFastTiles: the 24-bit multiply of the tile row is exact.)
+__device__ __forceinline__ bool simple_taf_fields(const FastGeom &G, int x, int y, uint32_t p, uint32_t t, uint32_t t0lo, uint32_t &tile,
+                                                  uint32_t &word, uint32_t &window)
+{
+    const uint32_t relu = t - t0lo;
+    uint32_t z = __umulhi(relu, G.win_magic); // floor(rel / win) or one less
+    uint32_t rem = relu - z * G.win;
+    if (rem >= G.win) { ++z; rem -= G.win; }
+    if (z >= (uint32_t)G.n_windows) { z = (uint32_t)G.n_windows - 1u; rem = G.win; } // t == end of the last window
+    const uint32_t tw1 = (1u << G.twl) - 1u, th1 = (1u << G.thl) - 1u;
+    const uint32_t cell = (((((uint32_t)y & th1) << G.twl) | ((uint32_t)x & tw1)) << 1) | p;
+    tile = ((__umul24((uint32_t)y >> G.thl, (uint32_t)G.tiles_x) + ((uint32_t)x >> G.twl)) << G.bin_shift) | ((cell >> 8) & (uint32_t)G.bin_mask);
+    window = z;
+    word = (rem << (kCellBits + G.wb)) | (z << kCellBits) | cell;
+    return !(t < t0lo || relu > G.span);
+}
+
 template <bool HAS_MAP, bool EV = false, bool SIMPLE = false, int SAE = 0>
 __device__ __forceinline__ FastEv fast_decode(const FastGeom &G, uint2 r, long long t0)
 {
@@ -279,12 +310,7 @@ __device__ __forceinline__ FastEv fast_decode(const FastGeom &G, uint2 r, long l
         y = G.ymap[y];
     }
     if (SAE == 1 && (x >= G.W || y >= G.H_full)) return o; // generate_surfaceofactiveevents.py:72
-    if (x >= G.W || y >= G.H_full) {
-        const long long flat = (long long)x + (long long)G.W * y;
-        if (flat >= (long long)G.H_full * G.W) { o.err = ST_INDEX; return o; }
-        y = (int)(flat / G.W);
-        x = (int)(flat - (long long)y * G.W);
-    }
+    if (!fast_alias(G, x, y)) { o.err = ST_INDEX; return o; }
     if (SIMPLE) {
         const uint32_t t0lo = (uint32_t)t0, relu = r.x - t0lo;
         if (EV) {
@@ -296,16 +322,11 @@ __device__ __forceinline__ FastEv fast_decode(const FastGeom &G, uint2 r, long l
             o.word = (relu << kCellBits) | celle;
             return o;
         }
-        if (r.x < t0lo || relu > G.span) { o.err = ST_SPAN; return o; }
-        uint32_t z = __umulhi(relu, G.win_magic); // floor(rel / win) or one less
-        uint32_t rem = relu - z * G.win;
-        if (rem >= G.win) { ++z; rem -= G.win; }
-        if (z >= (uint32_t)G.n_windows) { z = (uint32_t)G.n_windows - 1u; rem = G.win; } // t == end of the last window
-        const int tw1 = (1 << G.twl) - 1, th1 = (1 << G.thl) - 1;
-        const uint32_t cell = (uint32_t)((((y & th1) << G.twl) | (x & tw1)) << 1) | p;
-        o.tile = (((y >> G.thl) * G.tiles_x + (x >> G.twl)) << G.bin_shift) | (int)((cell >> 8) & (uint32_t)G.bin_mask);
-        o.window = z;
-        o.word = (rem << (kCellBits + G.wb)) | (z << kCellBits) | cell;
+        uint32_t tile, word, window; // (kf_scatter_cm's LEAN phase A calls the same two helpers without the early returns)
+        if (!simple_taf_fields(G, x, y, p, r.x, t0lo, tile, word, window)) { o.err = ST_SPAN; return o; }
+        o.tile = (int)tile;
+        o.window = window;
+        o.word = word;
         return o;
     }
     y -= G.y_lo; // row-stripe sharding: another rank owns the rows outside [y_lo, y_lo + H)
@@ -799,7 +820,11 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(MAXB > kMax
     __shared__ uint32_t wtot[kFW];
     __shared__ unsigned long long wg_seen;
     __shared__ int serr;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    // LEAN (TAF calls with the SIMPLE decode: the headline's form): phase A below decodes without early returns, and wv goes
+    // through readfirstlane, so that the compiler knows a wavefront's run (src, nloc, its counter row) is wave-uniform and keeps
+    // it in SGPRs.  (Not in the other forms: there the extra SGPRs cost spills -- DESIGN.md 3.11.)
+    constexpr bool LEAN = SIMPLE && !EV && !HAS_MAP && SAE == 0;
+    const int tid = threadIdx.x, lane = tid & 63, wv = LEAN ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
     SPROF_INIT();
     const int chunk = (int)chunk_of_block(blockIdx.x, gridDim.x);
     const int s = seq_of_chunk(S, chunk);
@@ -837,12 +862,10 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(MAXB > kMax
     constexpr int kAhead = MAXB > FRLW_SCATTER_AHEAD ? FRLW_SCATTER_AHEAD : MAXB;
     uint2 q[MAXB];
     const uint2 *src = G.data + wave_begin;
+    const uint32_t last = nloc - 1u;
     if (nloc > 0) { // wave-uniform; no load under a lane condition: lanes behind the run's end re-read its last event
 #pragma unroll
-        for (int j = 0; j < kAhead; ++j) {
-            const uint32_t i = (uint32_t)(j * kWave + lane);
-            q[j] = src[i < nloc ? i : nloc - 1u];
-        }
+        for (int j = 0; j < kAhead; ++j) q[j] = src[min((uint32_t)(j * kWave + lane), last)];
     }
     int pre_err = 0;
     // the per-call value table, spread over the grid while the event loads fly (generate_taf.py:215,:26 /
@@ -867,23 +890,42 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(MAXB > kMax
     SPROF(0);
     SPROF(1);
     // ---- phase A: stream rank of every event inside (wavefront, bin), one returning LDS atomic each (lane order = stream order)
+    // LEAN: fast_decode<false, false, true>'s two helpers without its early returns -- every value is computed for every lane and
+    // one mask `ok` decides, so the hot path has no nest of exec-mask branches with their default-value moves.  Same records,
+    // flags and window masks as fast_decode.
     uint32_t where[MAXB], word[MAXB];
     unsigned long long wseen = 0ull;
     int err = pre_err;
+    const uint32_t t0lo = (uint32_t)t0;
 #pragma unroll
     for (int j = 0; j < MAXB; ++j) {
         where[j] = 0xffffffffu;
         word[j] = 0u;
         if (j + kAhead < MAXB) {
-            if (nloc > 0 && j + kAhead < G.bpw) { // wave-uniform
-                const uint32_t i2 = (uint32_t)((j + kAhead) * kWave + lane);
-                q[j + kAhead] = src[i2 < nloc ? i2 : nloc - 1u];
-            }
+            if (nloc > 0 && j + kAhead < G.bpw) // wave-uniform
+                q[j + kAhead] = src[min((uint32_t)((j + kAhead) * kWave + lane), last)];
             asm volatile("" ::: "memory"); // (the request stays HERE: hoisted to the top it is the burst again)
         }
         if (j < G.bpw) {
             const uint32_t i = (uint32_t)(j * kWave + lane);
-            if (i < nloc) {
+            if (LEAN) {
+                if (nloc > 0) { // wave-uniform: an empty run has loaded nothing
+                    int x = (int)(q[j].y & 16383u), y = (int)((q[j].y >> 14) & 16383u);
+                    const uint32_t p = (q[j].y >> 28) & 1u;
+                    const bool ib = !fast_alias(G, x, y);
+                    uint32_t tile, w, z;
+                    const bool sb = !simple_taf_fields(G, x, y, p, q[j].x, t0lo, tile, w, z);
+                    const bool live = i < nloc, ok = live && !ib && !sb;
+                    if (live && !ok) err |= ib ? ST_INDEX : ST_SPAN; // (no lane of a valid call)
+                    uint32_t r = 0u;
+                    if (ok) {
+                        r = atomicAdd(&wcnt[tile], 1u);
+                        wseen |= 1ull << z;
+                    }
+                    where[j] = ok ? (tile << 16) | r : 0xffffffffu;
+                    word[j] = w;
+                }
+            } else if (i < nloc) {
                 const FastEv o = fast_decode<HAS_MAP, EV, SIMPLE, SAE>(G, q[j], t0);
                 err |= o.err;
                 if (o.tile >= 0) {
@@ -948,8 +990,15 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(MAXB > kMax
     __syncthreads();
     SPROF(5);
     // ---- phase D: the staged chunk leaves as it is, one linear sweep into the chunk's own stretch of rec[]
+    // (16-byte LDS reads and global stores where both ends are 16-byte aligned -- every chunk of a one-sequence call -- then the
+    // last total % 4 words one by one; the layout of rec[] is the same either way)
     uint32_t *dst = records + (chunk_begin - S.ev0[0]);
-    for (uint32_t qi = tid; qi < total; qi += kFT) dst[qi] = stage[qi];
+    uint32_t q4 = 0u;
+    if (((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(stage)) & 15u) == 0u) {
+        q4 = total & ~3u;
+        for (uint32_t qi = 4u * tid; qi < q4; qi += 4u * kFT) *reinterpret_cast<uint4 *>(dst + qi) = *reinterpret_cast<const uint4 *>(stage + qi);
+    }
+    for (uint32_t qi = q4 + tid; qi < total; qi += kFT) dst[qi] = stage[qi];
     SPROF(6);
     SPROF_DRAIN();
     SPROF(7);
