@@ -28,6 +28,8 @@
 
 #include <atomic>
 #include <stddef.h>
+#include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <type_traits>
 
@@ -35,13 +37,6 @@ using namespace frlw;
 
 namespace {
 
-// TAF through the tile walk (kf_taf_tile) instead of kf_split_whole + kf_taf_walk: bit-identical, 23 % less HBM traffic,
-// but measured SLOWER on MI355X (141 vs 121 us of tile work at 10 M events) -- so it is opt-in
-// (frlw_tuning_t::taf_tile_walk), and the Event Volume batch path, which has no other tile kernel, is its user.
-#ifndef FRLW_TAF_TILE_WALK
-#define FRLW_TAF_TILE_WALK 0
-#endif
-constexpr bool kTafTileWalk = FRLW_TAF_TILE_WALK != 0;
 constexpr int kFT = 1024;                 // threads of every workgroup here
 constexpr int kFW = kFT / kWave;          // 16 wavefronts
 constexpr int kCellBits = 12;
@@ -86,7 +81,6 @@ struct FastGeom {
     int chunk_ev; // events per chunk (one scatter workgroup), a multiple of 16, <= 8192
     int run;      // events per wavefront of the scatter workgroup = chunk_ev / 16
     long long n_total; // records in the array (loads never go past it)
-    int order_check;   // TAF: flag sequences whose window index ever decreases (only the tile walk needs to know)
     int y_lo, H_full;  // row-stripe sharding of one frame: this call encodes rows [y_lo, y_lo + H) of an H_full-row frame; events
                        // of other rows are skipped (not an error); H_full == H, y_lo == 0: the whole frame
     int n_windows, wb;
@@ -103,8 +97,6 @@ struct FastHeader {
     uint32_t filtered_tiles; // diagnostic: sub-tiles whose records were not window-sorted (unsorted stream)
     unsigned long long wmask[kMaxSeq]; // bit w set <=> window w of the sequence holds at least one event
     uint32_t mul_bad; // != 0: float(r * (1 / den)) differs from float(r / den) for some r in [0, win]: use the table
-    uint32_t unsorted[kMaxSeq]; // != 0: somewhere in the sequence an event's window is lower than its predecessor's (the
-                                // tile walk needs window-sorted lists; such a sequence takes the split + sub-tile kernels)
     // chunk-major partition: where the next (sequence, tile) list goes in rec2[] / the next split segment id (the header is
     // zeroed by a memset node in front of kf_scatter_cm; placement order is whatever order the workgroups arrive in -- the
     // lists themselves, and everything computed from them, do not depend on it)
@@ -199,6 +191,32 @@ bool fast_plan(long long n, int n_seq, int H, int W, FastPlan &p, int direct_mod
     return true;
 }
 
+// The workspace layout: ONE list of tables, laid out from (chunk count, slab count, events, window, plan).  fast_layout calls it
+// with the call's own counts, the size query (frlw_taf_batch_workspace_bytes) with its upper bounds: what the query budgets
+// is by construction what a call lays out.
+void layout_offsets(FastPlan &p, size_t chunks, size_t slabs, long long n, size_t win)
+{
+    const size_t n_rec = (size_t)(n > 0 ? n : 1);
+    size_t off = kHeaderBytes;
+    auto take = [&off](size_t bytes) { const size_t at = off; off = align_up(off + bytes, 256); return at; };
+    p.max_segs = 2 * (int)(n / kSplitSeg) + 1; // tiles above the whole-tile limit (>= one segment): full segments + one partial each
+    p.off_counts = take(chunks * p.TB * 4);
+    p.off_slabtot = take(slabs * p.TB * 4);
+    p.off_base = take((size_t)(p.pairs_b + 1) * 4);
+    p.off_sub = take(((size_t)p.pairs * kFW + 1) * 4);
+    p.off_seg0 = take((size_t)(p.pairs_b + 1) * 4);
+    p.off_segcnt = take((size_t)p.max_segs * kFW * 4);
+    p.off_errs = take(chunks * 4);
+    p.off_tlut = take((win + 1) * 4);
+    p.off_records = take(n_rec * 4);
+    p.off_records2 = take(n_rec * 4);
+    p.off_sub_end = take(((size_t)p.pairs * kFW + 1) * 4);
+    p.off_segdesc = take((size_t)p.max_segs * 4);
+    p.off_wst = take((size_t)p.pairs * kFW * (FRLW_MAX_WINDOWS + 1) * 4);
+    p.off_wst_flag = take((size_t)p.pairs * 4);
+    p.bytes = off;
+}
+
 // per-sequence chunk / slab tables + workspace layout
 bool fast_layout(const int64_t *seq_offsets, const int64_t *t_start, int n_seq, FastPlan &p, SeqTab &S, uint32_t win)
 {
@@ -223,24 +241,7 @@ bool fast_layout(const int64_t *seq_offsets, const int64_t *t_start, int n_seq, 
     S.ev0[n_seq] = seq_offsets[n_seq];
     p.chunks = c;
     p.slabs = sl;
-    const long long n = seq_offsets[n_seq] - seq_offsets[0];
-    size_t off = kHeaderBytes;
-    p.off_counts = off;  off = align_up(off + (size_t)(c > 0 ? c : 1) * p.TB * 4, 256);
-    p.off_slabtot = off; off = align_up(off + (size_t)(sl > 0 ? sl : 1) * p.TB * 4, 256);
-    p.off_base = off;    off = align_up(off + (size_t)(p.pairs_b + 1) * 4, 256);
-    p.off_sub = off;     off = align_up(off + ((size_t)p.pairs * kFW + 1) * 4, 256);
-    p.max_segs = 2 * (int)(n / kSplitSeg) + 1; // tiles above the whole-tile limit (>= one segment): full segments + one partial each
-    p.off_seg0 = off;    off = align_up(off + (size_t)(p.pairs_b + 1) * 4, 256);
-    p.off_segcnt = off;  off = align_up(off + (size_t)p.max_segs * kFW * 4, 256);
-    p.off_errs = off;    off = align_up(off + (size_t)(c > 0 ? c : 1) * 4, 256);
-    p.off_tlut = off;    off = align_up(off + (size_t)(win + 1) * 4, 256);
-    p.off_records = off; off = align_up(off + (size_t)(n > 0 ? n : 1) * 4, 256);
-    p.off_records2 = off; off = align_up(off + (size_t)(n > 0 ? n : 1) * 4, 256);
-    p.off_sub_end = off; off = align_up(off + ((size_t)p.pairs * kFW + 1) * 4, 256);
-    p.off_segdesc = off; off = align_up(off + (size_t)p.max_segs * 4, 256);
-    p.off_wst = off;     off = align_up(off + (size_t)p.pairs * kFW * (FRLW_MAX_WINDOWS + 1) * 4, 256);
-    p.off_wst_flag = off; off = align_up(off + (size_t)p.pairs * 4, 256);
-    p.bytes = off;
+    layout_offsets(p, (size_t)c, (size_t)sl, seq_offsets[n_seq] - seq_offsets[0], win); // (every sequence has a chunk: c, sl >= 1)
     return true;
 }
 
@@ -541,7 +542,7 @@ __global__ __launch_bounds__(kFT) void kf_tilescan(SeqTab S, uint32_t *slabtot, 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int pairs = S.n_seq * T; // (T = bins per sequence: tiles, or sub-tiles in the direct mode)
     if (tid == 0) { hdr->status = 0; hdr->filtered_tiles = 0u; hdr->mul_bad = 0u; }
-    if (tid < kMaxSeq) { hdr->wmask[tid] = 0ull; hdr->unsorted[tid] = 0u; }
+    if (tid < kMaxSeq) hdr->wmask[tid] = 0ull;
     __syncthreads();
     {
         int e = 0;
@@ -614,8 +615,7 @@ __host__ __device__ inline size_t scatter_lds_bytes(int T, int chunk)
     return (size_t)kFW * T * 4 + (size_t)(T + 2) * 4 + (size_t)chunk * 4 + (size_t)chunk * 2 + 16;
 }
 
-template <bool HAS_MAP, bool EV = false, bool ORDER = false, bool SIMPLE = false> // ORDER: flag sequences whose window index ever decreases (a
-// template parameter on purpose: as a run-time flag the mere presence of the check cost this kernel 35 %, measured)
+template <bool HAS_MAP, bool EV = false, bool SIMPLE = false>
 __global__ __launch_bounds__(kFT) void kf_scatter(FastGeom G, SeqTab S, const uint32_t *counts, const uint32_t *slabtot,
                                                   const uint32_t *base, uint32_t *records, FastHeader *hdr)
 {
@@ -641,11 +641,6 @@ __global__ __launch_bounds__(kFT) void kf_scatter(FastGeom G, SeqTab S, const ui
     const long long left = S.ev0[s + 1] - wave_begin;
     const uint32_t nloc = left < (long long)G.run ? (uint32_t)(left < 0 ? 0 : left) : (uint32_t)G.run;
     const long long t0 = S.t0[s];
-    // the event in front of this wavefront's run (same sequence), for the window-order check below: requested first, so
-    // that it is back first (loads return in order)
-    uint2 qprev = make_uint2(0u, 0u);
-    const bool has_prev = ORDER && nloc > 0 && wave_begin > S.ev0[s];
-    if (ORDER && nloc > 0) qprev = G.data[has_prev ? wave_begin - 1 : wave_begin];
     uint2 q[kMaxBpw];
     if (nloc > 0) { // wave-uniform.  No load under a lane condition (each would wait for its own data: eight serialized round
                     // trips): lanes behind the run's end re-read its last event and are masked by `i < nloc` below
@@ -667,17 +662,12 @@ __global__ __launch_bounds__(kFT) void kf_scatter(FastGeom G, SeqTab S, const ui
     // program order, so the returned count is the number of earlier events of the wavefront's run in the same tile.
     uint32_t where[kMaxBpw], word[kMaxBpw];
     unsigned long long wseen = 0ull;
-    // window of the event in front of this wavefront's run (same sequence), for the order check below
-    uint32_t carry = 0u;
-    if (has_prev) carry = fast_decode<HAS_MAP, EV, SIMPLE>(G, qprev, t0).window;
-    bool backwards = false;
 #pragma unroll
     for (int j = 0; j < kMaxBpw; ++j) {
         where[j] = 0xffffffffu;
         word[j] = 0u;
         if (j < G.bpw) {
             const uint32_t i = (uint32_t)(j * kWave + lane);
-            uint32_t win_j = 0xffffffffu; // lanes behind the run's end: larger than any window
             if (i < nloc) {
                 const FastEv o = fast_decode<HAS_MAP, EV, SIMPLE>(G, q[j], t0);
                 if (o.tile >= 0) {
@@ -685,29 +675,10 @@ __global__ __launch_bounds__(kFT) void kf_scatter(FastGeom G, SeqTab S, const ui
                     where[j] = ((uint32_t)o.tile << 16) | r;
                     word[j] = o.word;
                     wseen |= 1ull << o.window;
-                    win_j = o.window;
-                }
-            }
-            if (ORDER) { // does the stream ever step back into an earlier window?  (the tile walk relies on window-sorted lists)
-                // Usual case: the 64 events of the batch lie in ONE window that is not below the previous batch's last --
-                // two lane reads and a ballot.  Otherwise (a window boundary inside the batch, an event that was not
-                // encoded, the ragged end of a run) every lane looks at its left neighbour.
-                const uint32_t w_first = (uint32_t)__builtin_amdgcn_readfirstlane((int)win_j);
-                if (__ballot(win_j != w_first) == 0ull) {
-                    if (w_first != 0xffffffffu) { backwards |= w_first < carry; carry = w_first; }
-                } else {
-                    uint32_t prev = (uint32_t)__shfl_up((int)win_j, 1);
-                    if (lane == 0) prev = carry;
-                    // lanes without an event (0xffffffff) neither compare nor serve as a neighbour: the ragged end of a run
-                    // only has them behind its last event, an error event voids the whole call anyway
-                    backwards |= win_j != 0xffffffffu && prev != 0xffffffffu && win_j < prev;
-                    const unsigned long long have = __ballot(win_j != 0xffffffffu);
-                    if (have) carry = (uint32_t)__builtin_amdgcn_readlane((int)win_j, 63 - __builtin_clzll(have));
                 }
             }
         }
     }
-    if (ORDER && __ballot(backwards) && lane == 0) atomicOr(&hdr->unsorted[s], 1u);
     __syncthreads();
     // ---- phase B: per tile, exclusive prefix of the 16 wavefront counts; chunk-local offsets of the tiles
     uint32_t mine = 0; // records of tile `tid` in this chunk
@@ -1041,9 +1012,6 @@ struct TileP {
     uint32_t *segcnt;      // [segments][16] records of every sub-tile in a segment, then their offsets inside the sub-tile
     int pairs;
     int direct;            // 1: rec2 / sub are the scatter's own output (sub-tile bins): no split kernel has run
-    int skip_whole;        // 1: tiles up to the whole-tile limit are NOT re-sorted (a tile-walk kernel splits them in LDS) ...
-    int tile_walk;         // ... TAF: unless their sequence is not window-sorted (hdr->unsorted)
-    int first_block;       // kf_split_whole: block b does the work of block b + first_block
     int seg_grid;          // segment workgroups launched (they stride over the segments: most calls have none)
     uint32_t tile_max;     // tiles with more records than this go through the segment split
     const float *tlut;
@@ -1274,9 +1242,8 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     // wait for the header's round trip; the directory lies at addresses the plan fixes, reading it is safe whatever the status)
     const int32_t status0 = q.hdr->status;
     if (!CM && status0 != 0) return;
-    const int blk = (int)blockIdx.x + q.first_block;
+    const int blk = (int)blockIdx.x;
     if (!CM && blk >= q.pairs) { // the blocks behind the tiles: one segment of a skewed tile each (4b, counting)
-        if (q.first_block && blk == q.pairs && tid == 0) q.sub[(long long)q.pairs * kFW] = q.base[q.pairs]; // (the last tile's block is not there to do it)
         const uint32_t nseg = q.seg0[q.pairs];
         for (uint32_t seg = (uint32_t)(blk - q.pairs); seg < nseg; seg += (uint32_t)q.seg_grid) {
             split_count_segment(q, seg, wtot);
@@ -1357,8 +1324,7 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         beg = q.base[g];
         const uint32_t end = q.base[g + 1];
         if (g == q.pairs - 1 && tid == 0) q.sub[(long long)q.pairs * kFW] = end; // end of the last sub-tile's list
-        if (end - beg > whole_max_of(q.pairs) || q.skip_whole) return; // a skewed tile (or a call with few tiles): left to the segment kernels below
-        if (q.tile_walk && q.hdr->unsorted[g / q.T] == 0u) return;     // split in LDS by kf_taf_tile
+        if (end - beg > whole_max_of(q.pairs)) return; // a skewed tile (or a call with few tiles): left to the segment kernels below
         n = end - beg;
         if (n == 0u) {
             if (tid < kFW) q.sub[(long long)g * kFW + tid] = beg;
@@ -1799,7 +1765,6 @@ __global__ __launch_bounds__(kWalkThreads) __attribute__((amdgpu_waves_per_eu(8,
     }
     if (status0 != 0) return; // data-dependent error: nothing is written (the caller re-runs the general path)
     WPROF_INIT();
-    if (q.tile_walk && q.hdr->unsorted[s] == 0u && q.base[g + 1] - q.base[g] <= q.tile_max) return; // done by kf_taf_tile
     const int K = K8 ? 8 : q.K;
     const int NW = q.n_windows;
     const uint32_t *list = q.rec2; // where the sweeps below read the list (CMD: LDS when the list fits)
@@ -2166,16 +2131,7 @@ __global__ __launch_bounds__(kWalkThreads) __attribute__((amdgpu_waves_per_eu(8,
     WPROF_END();
 }
 
-// =====================================================================================================================
-// Tile walk: the second-level split done in LDS by the kernel that consumes it
-// =====================================================================================================================
-// kf_split_whole re-sorts a tile's records sub-tile-major through HBM (75 MB read + 41 MB written per 10 M events) only so
-// that the sub-tile kernel finds its list contiguous.  A tile-walk workgroup instead streams the tile's list (tile-major,
-// stream order, written by kf_scatter) in chunks, splits every chunk STABLY by sub-tile inside LDS with the same
-// lane-ordered tickets, and hands each sub-tile's piece to the wavefront that owns the sub-tile.  NW wavefronts per
-// workgroup = NW sub-tiles; 16 / NW workgroups ("parts") share a tile and each reads the whole list (from the XCD's L2:
-// the parts of a tile are placed on one XCD) but keeps only its own sub-tiles.
-//
+// ---- the ticket sort of one wavefront (kf_ev_sub) ------------------------------------------------------------------------
 // Wave-private pass (the core of kf_taf_walk's phase 1, factored out): up to 256 records of ONE sub-tile, in stream order,
 // become per-cell ordered segments -- a ticket per record from two-per-word 16-bit LDS counters (lane-ordered, so the
 // ticket is the stream rank inside the cell), a wave scan of the cell counts, values to sorted[offset(cell) + ticket] --
@@ -2301,277 +2257,17 @@ __device__ __forceinline__ void wave_segments(const WavePass &P, const uint32_t 
     }
 }
 
-// In-LDS stable split of one chunk of a tile's list.  NT threads, RPT records per thread: record u * NT + tid of the chunk
-// (stream order = (round u, wavefront, lane)).  Every record of one of this workgroup's NW sub-tiles takes a ticket from
-// the (round, wavefront, sub-tile) counter -- lane-ordered -- wavefront b scans sub-tile b's RPT * NW counters in stream
-// order, the sub-tile totals are scanned by every wavefront for itself, and the records land sub-tile-major in stage[].
-// Returns through sb / nb the start and length of THIS wavefront's sub-tile in stage[].  Four workgroup barriers.
-template <int NW, int RPT>
-struct TileSplit {
-    static constexpr int NT = NW * kWave;
-    static constexpr int CH = NT * RPT;
-    uint32_t scnt[RPT][NW][NW]; // [round][wavefront][sub-tile]
-    uint32_t btot[NW];
-    uint32_t stage[CH];
-};
-
-template <int NW, int RPT>
-__device__ __forceinline__ void tile_split(TileSplit<NW, RPT> &L, const uint32_t (&m)[RPT], const bool (&mine)[RPT], int part,
-                                           uint32_t &sb, uint32_t &nb)
-{
-    constexpr int NE = RPT * NW;
-    static_assert(NE <= kWave, "one wavefront scans a sub-tile's counters");
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    uint32_t rk[RPT];
-#pragma unroll
-    for (int u = 0; u < RPT; ++u) {
-        rk[u] = 0u;
-        if (mine[u]) rk[u] = atomicAdd(&L.scnt[u][wv][((m[u] >> 8) & 15u) - (uint32_t)(part * NW)], 1u);
-    }
-    __syncthreads();
-    {
-        uint32_t v = 0;
-        if (lane < NE) v = L.scnt[lane / NW][lane % NW][wv];
-        const uint32_t inc = wave_incl_scan(v);
-        if (lane < NE) L.scnt[lane / NW][lane % NW][wv] = inc - v;
-        if (lane == kWave - 1) L.btot[wv] = inc;
-    }
-    __syncthreads();
-    uint32_t ex;
-    {
-        const uint32_t t = lane < NW ? L.btot[lane] : 0u;
-        ex = wave_incl_scan(t) - t; // lane b: first slot of sub-tile b
-    }
-    sb = (uint32_t)__shfl((int)ex, wv);
-    nb = L.btot[wv];
-#pragma unroll
-    for (int u = 0; u < RPT; ++u) {
-        const uint32_t b = mine[u] ? ((m[u] >> 8) & 15u) - (uint32_t)(part * NW) : 0u;
-        const uint32_t base = (uint32_t)__shfl((int)ex, (int)b);
-        if (mine[u]) L.stage[base + L.scnt[u][wv][b] + rk[u]] = m[u];
-    }
-    __syncthreads();
-}
-
-// blockIdx -> (pair, part) with the parts of a pair on ONE XCD (blocks b and b + 8 share an XCD): the list is read from
-// HBM once and from that XCD's L2 by the other parts.
-template <int PARTS>
-__device__ __forceinline__ bool pair_part_of_block(int pairs, int &g, int &part)
-{
-    const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
-    part = q % PARTS;
-    g = (q / PARTS) * 8 + xcd;
-    return g < pairs;
-}
-
-// ---- Temporal Active Focus ---------------------------------------------------------------------------------------------
-// One workgroup = NW sub-tiles of one (sequence, tile) pair of a WINDOW-SORTED sequence (kf_scatter flags the others).
-// The tile's list is streamed once, in stream order; wavefront v keeps the FIFO rows of its 256 cells (four per lane) in
-// registers together with the running (sum, count) of the window it is in, and closes windows -- one FIFO step per cell,
-// generate_taf.py:27-49 -- whenever its records move on to a later window.  Replaces kf_split_whole + kf_taf_walk for the
-// tiles it takes: the sub-tile-major copy of the records never exists.
-struct TafWaveLds {
-    uint32_t cnt[kSubCells / 2];
-    uint16_t off[kSubCells];
-    float sorted[kSubCells];
-}; // 2 KB; at the end the uint8 staging of the wavefront's sub-tile: 2K planes x 128 pixels
-
-template <int NW, bool K8>
-__global__ __launch_bounds__(NW *kWave) void kf_taf_tile(TileP q)
-{
-    constexpr int RPT = 4, NT = NW * kWave, CH = NT * RPT, PARTS = kFW / NW;
-    __shared__ TileSplit<NW, RPT> L;
-    __shared__ __attribute__((aligned(16))) TafWaveLds wl[NW];
-    __shared__ uint32_t thr[kLeakyLevels];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    int g, part;
-    if (!pair_part_of_block<PARTS>(q.pairs, g, part)) return;
-    if (q.hdr->status != 0) return;
-    const int s = g / q.T, tile = g - s * q.T;
-    if (q.hdr->unsorted[s] != 0u) return; // kf_split_whole + kf_taf_walk
-    const uint32_t beg = q.base[g], end = q.base[g + 1];
-    if (end - beg > q.tile_max) return;   // skewed tile: segment split + kf_taf_walk
-    const int K = K8 ? 8 : q.K;
-    const int NWIN = q.n_windows;
-    for (int i = tid; i < kLeakyLevels; i += NT) thr[i] = q.leaky_thr[i];
-    for (int i = lane; i < kSubCells / 2; i += kWave) wl[wv].cnt[i] = 0u;
-    for (int i = tid; i < RPT * NW * NW; i += NT) (&L.scnt[0][0][0])[i] = 0u;
-    const WavePass P = {wl[wv].cnt, wl[wv].off, wl[wv].sorted};
-    const unsigned long long wmask = q.hdr->wmask[s];
-    const bool use_mul = q.hdr->mul_bad == 0u; // checked for every r of the domain by kf_hist
-    const double rcp = q.rcp;
-    const uint32_t wfield = (1u << q.wb) - 1u;
-    const int rshift = kCellBits + q.wb;
-    // the lane's four cells: cell 64 j + lane of sub-tile `sub` = pixel 128 sub + 32 j + lane / 2 of the tile, polarity lane & 1
-    const int sub = part * NW + wv;
-    const int ty = tile / q.tiles_x, tx = tile - ty * q.tiles_x;
-    const int x0 = tx << q.twl, y0 = ty << q.thl, tw1 = (1 << q.twl) - 1;
-    const long long plane = (long long)q.H * q.W;
-    const int pol = lane & 1;
-    float st[4][kMaxK], sum[4];
-    uint32_t num[4];
-    bool ok[4];
-    long long pix[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int pt = sub * (kSubCells / 2) + 32 * j + (lane >> 1);
-        const int py = y0 + (pt >> q.twl), px = x0 + (pt & tw1);
-        ok[j] = py < q.H && px < q.W;
-        pix[j] = (long long)py * q.W + px;
-        const float *srow = q.state + (((long long)s * plane + pix[j]) * 2 + pol) * K;
-#pragma unroll
-        for (int k = 0; k < kMaxK; ++k) st[j][k] = 0.0f;
-        if (ok[j]) {
-            if (K8) {
-                const float4 a = ((const float4 *)srow)[0], b = ((const float4 *)srow)[1];
-                st[j][0] = a.x; st[j][1] = a.y; st[j][2] = a.z; st[j][3] = a.w;
-                st[j][4] = b.x; st[j][5] = b.y; st[j][6] = b.z; st[j][7] = b.w;
-            } else {
-#pragma unroll
-                for (int k = 0; k < kMaxK; ++k)
-                    if (k < K) st[j][k] = srow[k];
-            }
-        }
-        sum[j] = 0.0f;
-        num[j] = 0u;
-    }
-    int cur_w = 0; // wave-uniform: windows below it are closed for this wavefront's cells
-    auto close_upto = [&](int w) { // FIFO steps of windows cur_w .. w - 1 (skipped when empty in the whole sequence, :40-41)
-#pragma nounroll
-        for (; cur_w < w; ++cur_w) {
-            const bool has = (wmask >> cur_w) & 1ull;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                fifo_step(st[j], K, has, num[j], fifo_mean(num[j], sum[j]));
-                sum[j] = 0.0f;
-                num[j] = 0u;
-            }
-        }
-    };
-    uint32_t m[RPT], nx[RPT];
-    // (loads without lane conditions -- a conditional load waits for its own data: indices are clamped, values masked)
-#pragma unroll
-    for (int u = 0; u < RPT; ++u) {
-        const uint32_t i = beg + (uint32_t)(u * NT + tid);
-        nx[u] = 0xffffffffu;
-        if (end > beg) { const uint32_t v = q.rec[i < end ? i : end - 1u]; nx[u] = i < end ? v : 0xffffffffu; }
-    }
-    __syncthreads();
-    for (uint32_t c0 = beg; c0 < end; c0 += CH) {
-        bool mine[RPT];
-#pragma unroll
-        for (int u = 0; u < RPT; ++u) {
-            m[u] = nx[u];
-            mine[u] = m[u] != 0xffffffffu && (int)((m[u] >> 8) & 15u) / NW == part;
-            const uint32_t i = c0 + CH + (uint32_t)(u * NT + tid); // the next chunk's loads fly during this one's passes
-            const uint32_t v = q.rec[i < end ? i : end - 1u];
-            nx[u] = i < end ? v : 0xffffffffu;
-        }
-        uint32_t sb, nb;
-        tile_split<NW, RPT>(L, m, mine, part, sb, nb);
-        for (int i = tid; i < RPT * NW * NW; i += NT) (&L.scnt[0][0][0])[i] = 0u; // dead since the placement; next chunk's tickets
-        for (uint32_t p0 = 0; p0 < nb; p0 += 256) {
-            uint32_t pm[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const uint32_t i = p0 + (uint32_t)(u * kWave + lane);
-                pm[u] = i < nb ? L.stage[sb + i] : 0xffffffffu;
-            }
-            // the pass's records are window-sorted: first and last record give its window range
-            const uint32_t last = nb - p0 < 256u ? nb - 1u : p0 + 255u;
-            const int wlo = (int)((L.stage[sb + p0] >> kCellBits) & wfield), whi = (int)((L.stage[sb + last] >> kCellBits) & wfield);
-#pragma nounroll
-            for (int w = wlo; w <= whi; ++w) {
-                close_upto(w);
-                uint32_t sel[4], n[4], o[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    sel[u] = (pm[u] != 0xffffffffu && (int)((pm[u] >> kCellBits) & wfield) == w) ? pm[u] : 0xffffffffu;
-                wave_sort(P, sel, lane,
-                          [&](uint32_t rw) {
-                              const uint32_t r = rw >> rshift; // t - 1 with t = (t - t_min) / (w + 1e-8) in f64 (generate_taf.py:215, :26)
-                              return use_mul ? (float)((double)r * rcp) - 1.0f : q.tlut[r];
-                          }, n, o);
-                wave_segments(P, n, o, [&](int j, float v, bool live) {
-                    const float t = sum[j] + v; // sum += t - 1 in stream order, generate_taf.py:26
-                    sum[j] = live ? t : sum[j];
-                });
-#pragma unroll
-                for (int j = 0; j < 4; ++j) num[j] += n[j];
-                LDS_FENCE();
-            }
-        }
-        __syncthreads(); // stage[] and scnt[] are reused by the next chunk
-    }
-    close_upto(NWIN);
-
-    // ---- write-out: state, optional f32 view (2K, H, W), optional uint8 leaky transform (K, 2, H, W)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        if (!ok[j]) continue;
-        float *srow = q.state + (((long long)s * plane + pix[j]) * 2 + pol) * K;
-        if (K8) {
-            ((float4 *)srow)[0] = make_float4(st[j][0], st[j][1], st[j][2], st[j][3]);
-            ((float4 *)srow)[1] = make_float4(st[j][4], st[j][5], st[j][6], st[j][7]);
-        } else {
-#pragma unroll
-            for (int k = 0; k < kMaxK; ++k)
-                if (k < K) srow[k] = st[j][k];
-        }
-        if (q.view_f32) {
-            float *vw = q.view_f32 + (long long)s * 2 * K * plane + pix[j];
-#pragma unroll
-            for (int k = 0; k < kMaxK; ++k)
-                if (k < K) vw[(long long)(2 * k + pol) * plane] = st[j][k]; // generate_taf.py:55
-        }
-    }
-    if (q.out_u8) {
-        uint8_t *ob = (uint8_t *)&wl[wv]; // [2K planes][128 pixels of the sub-tile]; the wave's pass buffers are dead
-        LDS_FENCE();
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            uint8_t lv[kMaxK];
-            leaky_u8_lookup_n<kMaxK>(st[j], thr, lv);
-#pragma unroll
-            for (int k = 0; k < kMaxK; ++k) {
-                if (k < K) {
-                    const int ko = q.flip ? (K - 1 - k) : k;
-                    ob[(2 * ko + pol) * (kSubCells / 2) + 32 * j + (lane >> 1)] = lv[k];
-                }
-            }
-        }
-        LDS_FENCE();
-        // the (K, 2, H, W) volume leaves plane by plane in 16-pixel pieces: one 16-byte store where the row allows
-        for (int c = lane; c < 2 * K * 8; c += kWave) {
-            const int pl = c >> 3, piece = c & 7;
-            const int p16 = sub * (kSubCells / 2) + 16 * piece;
-            const int y = y0 + (p16 >> q.twl), x = x0 + (p16 & tw1);
-            if (y >= q.H || x >= q.W) continue;
-            const uint8_t *src = ob + pl * (kSubCells / 2) + 16 * piece;
-            uint8_t *dst = q.out_u8 + ((long long)s * 2 * K + pl) * plane + (long long)y * q.W + x;
-            if (x + 16 <= q.W && (((uintptr_t)dst) & 15u) == 0) {
-                *(uint4 *)dst = *(const uint4 *)src;
-            } else {
-                const int nv = q.W - x < 16 ? q.W - x : 16;
-                for (int e = 0; e < nv; ++e) dst[e] = src[e];
-            }
-        }
-    }
-}
-
 // ---- Event Volume ------------------------------------------------------------------------------------------------------
 struct EvTileP {
     int H, W, twl, thl, tiles_x, T, bins;
     uint32_t win;
     double rcp;           // FastGeom::rcp
-    const uint32_t *rec;  // tile-major records (scatter output)
-    const uint32_t *rec2; // sub-tile-major (segment split), for the tiles the tile walk leaves alone
+    const uint32_t *rec2; // sub-tile-major records: the lists kf_ev_sub walks (chunk-major + direct: where a consumer books space for a long list)
     const uint32_t *base; // [pairs + 1]
     const uint32_t *sub;  // [pairs * 16 + 1]
     const uint32_t *sub_end; // TileP::sub_end
     int pairs;
     int direct;           // TileP::direct
-    uint32_t tile_max;    // tiles with more records go through the segment split + kf_ev_sub
     const float *tlut;    // tlut[r] = float(r / window)
     FastHeader *hdr;
     float *out_f32;       // (B, 2 * bins, H, W) or NULL
@@ -2672,70 +2368,6 @@ __device__ __forceinline__ void ev_store(const EvTileP &q, int s, int tile, int 
     for (int j = 0; j < 4; ++j) ev_store_cells<BINS>(q, s, tile, sub, lane, j, acc[j]);
 }
 
-// One workgroup = NW sub-tiles of one (sequence, tile) pair; see the section header.
-template <int NW, int BINS>
-__global__ __launch_bounds__(NW *kWave) void kf_ev_tile(EvTileP q)
-{
-    constexpr int RPT = 4, NT = NW * kWave, CH = NT * RPT, PARTS = kFW / NW;
-    __shared__ TileSplit<NW, RPT> L;
-    __shared__ uint32_t s_cnt[NW][kSubCells / 2];
-    __shared__ uint16_t s_off[NW][kSubCells];
-    __shared__ __attribute__((aligned(8))) float s_sorted[NW][2 * kSubCells + 2];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    int g, part;
-    if (!pair_part_of_block<PARTS>(q.pairs, g, part)) return;
-    if (q.hdr->status != 0) return;
-    const uint32_t beg = q.base[g], end = q.base[g + 1];
-    if (end - beg > q.tile_max) return; // skewed tile: segment split + kf_ev_sub
-    if (lane < 2) s_sorted[wv][2 * kSubCells + lane] = 0.0f; // the all-zero pair behind the segments
-    const int s = g / q.T, tile = g - s * q.T;
-    for (int i = lane; i < kSubCells / 2; i += kWave) s_cnt[wv][i] = 0u;
-    for (int i = tid; i < RPT * NW * NW; i += NT) (&L.scnt[0][0][0])[i] = 0u;
-    const WavePass P = {s_cnt[wv], s_off[wv], s_sorted[wv]};
-    const bool use_mul = q.hdr->mul_bad == 0u;
-    const double rcp = q.rcp;
-    const float binsf = (float)q.bins;
-    float acc[4][BINS];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int k = 0; k < BINS; ++k) acc[j][k] = 0.0f;
-    uint32_t m[RPT], nx[RPT];
-    // (loads without lane conditions -- a conditional load waits for its own data: indices are clamped, values masked)
-#pragma unroll
-    for (int u = 0; u < RPT; ++u) {
-        const uint32_t i = beg + (uint32_t)(u * NT + tid);
-        nx[u] = 0xffffffffu;
-        if (end > beg) { const uint32_t v = q.rec[i < end ? i : end - 1u]; nx[u] = i < end ? v : 0xffffffffu; }
-    }
-    __syncthreads();
-    for (uint32_t c0 = beg; c0 < end; c0 += CH) {
-        bool mine[RPT];
-#pragma unroll
-        for (int u = 0; u < RPT; ++u) {
-            m[u] = nx[u];
-            mine[u] = m[u] != 0xffffffffu && (int)((m[u] >> 8) & 15u) / NW == part;
-            const uint32_t i = c0 + CH + (uint32_t)(u * NT + tid); // the next chunk's loads fly during this one's passes
-            const uint32_t v = q.rec[i < end ? i : end - 1u];
-            nx[u] = i < end ? v : 0xffffffffu;
-        }
-        uint32_t sb, nb;
-        tile_split<NW, RPT>(L, m, mine, part, sb, nb);
-        for (int i = tid; i < RPT * NW * NW; i += NT) (&L.scnt[0][0][0])[i] = 0u; // dead since the placement; next chunk's tickets
-        for (uint32_t p0 = 0; p0 < nb; p0 += 256) {
-            uint32_t pm[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const uint32_t i = p0 + (uint32_t)(u * kWave + lane);
-                pm[u] = i < nb ? L.stage[sb + i] : 0xffffffffu;
-            }
-            ev_pass<BINS>(P, pm, lane, q, use_mul, rcp, binsf, acc);
-        }
-        __syncthreads(); // stage[] and scnt[] are reused by the next chunk
-    }
-    ev_store<BINS>(q, s, tile, part * NW + wv, lane, acc);
-}
-
 // After the segment split (kf_split_whole's counting blocks + kf_split_place): one wavefront per sub-tile walks its own
 // contiguous list -- the skewed tiles of any call, and every tile of a call with few (sequence, tile) pairs.
 // CMD (chunk-major partition, direct mode): the wavefront first gathers its sub-tile's runs from the chunks' stretches of rec[]
@@ -2746,7 +2378,7 @@ constexpr int kEvListCap = 2048;  // records of a sub-tile's list kept in LDS pe
 template <int BINS, bool CMD = false>
 // (five wavefronts per SIMD where the registers allow it without spills -- the five-bin list walk, 102 -> 92 VGPRs: every
 // wavefront is a latency chain of its own, one more of them per SIMD hides more of it)
-__global__ __launch_bounds__(4 * kWave) __attribute__((amdgpu_waves_per_eu((BINS <= 5 && !CMD) ? 5 : 1, 8))) void kf_ev_sub(EvTileP q, int all_tiles, CmP cm, SeqTab S)
+__global__ __launch_bounds__(4 * kWave) __attribute__((amdgpu_waves_per_eu((BINS <= 5 && !CMD) ? 5 : 1, 8))) void kf_ev_sub(EvTileP q, CmP cm, SeqTab S)
 {
     __shared__ uint32_t s_cnt[4][kSubCells / 2];
     __shared__ uint16_t s_off[4][kSubCells];
@@ -2758,7 +2390,6 @@ __global__ __launch_bounds__(4 * kWave) __attribute__((amdgpu_waves_per_eu((BINS
     const int sg = blockIdx.x * 4 + wv;
     if (sg >= q.pairs * kFW || q.hdr->status != 0) return;
     const int g = sg / kFW, sub = sg - g * kFW;
-    if (!all_tiles && q.base[g + 1] - q.base[g] <= q.tile_max) return; // done by kf_ev_tile
     const int s = g / q.T, tile = g - s * q.T;
     for (int i = lane; i < kSubCells / 2; i += kWave) s_cnt[wv][i] = 0u;
     const WavePass P = {s_cnt[wv], s_off[wv], s_sorted[wv]};
@@ -3149,44 +2780,42 @@ __global__ __launch_bounds__(kFT) void kf_selftest_lane_order(int n_addr, int it
     if (fbad) atomicAdd(&out[2], fbad);
 }
 
+// one instance of the bin-major scatter: the dynamic-LDS attribute where the chunk needs more than the default 64 KB, then the launch
+template <bool HAS_MAP, bool EV, bool SIMPLE>
+void launch_scatter(const FastGeom &G, const SeqTab &S, const FastPlan &p, char *w8, hipStream_t st)
+{
+    const size_t lds_sc = scatter_lds_bytes(p.TB, p.chunk);
+    if (lds_sc > 64 * 1024)
+        (void)hipFuncSetAttribute((const void *)kf_scatter<HAS_MAP, EV, SIMPLE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sc);
+    hipLaunchKernelGGL((kf_scatter<HAS_MAP, EV, SIMPLE>), dim3(p.chunks), dim3(kFT), lds_sc, st, G, S, (const uint32_t *)(w8 + p.off_counts),
+                       (const uint32_t *)(w8 + p.off_slabtot), (const uint32_t *)(w8 + p.off_base), (uint32_t *)(w8 + p.off_records), (FastHeader *)w8);
+}
+
+// the histogram partition: kf_hist, the scans, kf_scatter
 template <bool HAS_MAP, bool EV = false>
 void launch_fast(const FastGeom &G, const SeqTab &S, const FastPlan &p, char *w8, hipStream_t st)
 {
     FastHeader *hdr = (FastHeader *)w8;
     uint32_t *counts = (uint32_t *)(w8 + p.off_counts);
     uint32_t *slabtot = (uint32_t *)(w8 + p.off_slabtot);
-    uint32_t *base = (uint32_t *)(w8 + p.off_base);
     int32_t *errs = (int32_t *)(w8 + p.off_errs);
     float *tlut = (float *)(w8 + p.off_tlut);
-    uint32_t *records = (uint32_t *)(w8 + p.off_records);
-    const size_t lds_sc = scatter_lds_bytes(p.TB, p.chunk);
-    if (lds_sc > 64 * 1024) {
-        (void)hipFuncSetAttribute((const void *)kf_scatter<HAS_MAP, EV, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sc);
-        if (!EV) (void)hipFuncSetAttribute((const void *)kf_scatter<HAS_MAP, EV, !EV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sc);
-    }
     const int hist_grid = p.chunks < 512 ? p.chunks : 512; // persistent: two workgroups per CU
-    const bool simple = !HAS_MAP && G.simple != 0 && !(!EV && G.order_check);
-    if (simple) {
-        if (lds_sc > 64 * 1024)
-            (void)hipFuncSetAttribute((const void *)kf_scatter<false, EV, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sc);
+    const bool simple = !HAS_MAP && G.simple != 0;
+    if (simple)
         hipLaunchKernelGGL((kf_hist<false, EV, true>), dim3(hist_grid), dim3(kFT), (size_t)p.TB * 4, st, G, S, counts, errs, tlut, p.chunks);
-    } else {
+    else
         hipLaunchKernelGGL((kf_hist<HAS_MAP, EV>), dim3(hist_grid), dim3(kFT), (size_t)p.TB * 4, st, G, S, counts, errs, tlut, p.chunks);
-    }
     const bool inline_slabs = (long long)p.slabs * p.TB <= kInlineSlabScan;
     if (!inline_slabs)
         hipLaunchKernelGGL(kf_slabscan, dim3((p.TB + kWave - 1) / kWave, p.slabs), dim3(kWave), 0, st, S, counts, p.TB, slabtot);
-    hipLaunchKernelGGL(kf_tilescan, dim3(1), dim3(kFT), 0, st, S, slabtot, p.TB, base, (uint32_t *)(w8 + p.off_seg0), hdr, errs,
+    hipLaunchKernelGGL(kf_tilescan, dim3(1), dim3(kFT), 0, st, S, slabtot, p.TB, (uint32_t *)(w8 + p.off_base), (uint32_t *)(w8 + p.off_seg0), hdr, errs,
                        p.chunks, inline_slabs ? counts : (uint32_t *)nullptr, p.slabs, p.direct);
-    if (simple)
-        hipLaunchKernelGGL((kf_scatter<false, EV, false, true>), dim3(p.chunks), dim3(kFT), lds_sc, st, G, S, counts, slabtot, base, records, hdr);
-    else if (!EV && G.order_check)
-        hipLaunchKernelGGL((kf_scatter<HAS_MAP, EV, !EV>), dim3(p.chunks), dim3(kFT), lds_sc, st, G, S, counts, slabtot, base, records, hdr);
-    else
-        hipLaunchKernelGGL((kf_scatter<HAS_MAP, EV, false>), dim3(p.chunks), dim3(kFT), lds_sc, st, G, S, counts, slabtot, base, records, hdr);
+    if (simple) launch_scatter<false, EV, true>(G, S, p, w8, st);
+    else launch_scatter<HAS_MAP, EV, false>(G, S, p, w8, st);
 }
 
-// the captured form's header reset (status, window masks, cursors): see launch_fast_cm
+// the captured form's header reset (status, window masks, cursors): see cm_epoch
 __global__ __launch_bounds__(256) void kf_header_reset(FastHeader *hdr)
 {
     uint32_t *h32 = (uint32_t *)hdr;
@@ -3194,52 +2823,64 @@ __global__ __launch_bounds__(256) void kf_header_reset(FastHeader *hdr)
     if (threadIdx.x == 0) *(uint32_t *)((char *)hdr + kStallOffset) = 0u; // (the captured form has no wait and no stall of its own)
 }
 
-// the chunk-major partition: ONE kernel (its first workgroup resets the header; a reset kernel in front of it inside a capture)
-template <bool HAS_MAP, bool EV = false>
-int launch_fast_cm(const FastGeom &G, const SeqTab &S, const FastPlan &p, char *w8, hipStream_t st)
+// The epoch kf_scatter_cm's first workgroup publishes behind its header reset: the next value of `counter`, with `range` OR-ed in
+// (the SAE path keeps a range of its own: never equal to a TAF / Event Volume call's epoch of the same process ... within 2^30
+// calls), never 0.
+// Inside a stream capture the kernel arguments are frozen into the graph node: a host-made epoch would already be the
+// published one on every replay after the first (workgroups could then OR their flags into the header BEFORE workgroup 0
+// zeroes it).  A captured call resets the header with a kernel node of its own and passes epoch 0 = "nobody resets, nobody waits".
+// (a kernel node, not hipMemsetAsync: a captured memset node of this runtime wrote a stale pattern into the header from its
+// second replay on -- measured; tests/test_taf_fast_gpu.py replays a captured encode three times)
+uint32_t cm_epoch(std::atomic<uint32_t> &counter, uint32_t range, FastHeader *hdr, hipStream_t st)
 {
-    FastHeader *hdr = (FastHeader *)w8;
-    uint32_t *dir = (uint32_t *)(w8 + p.off_counts);
-    float *tlut = (float *)(w8 + p.off_tlut);
-    uint32_t *records = (uint32_t *)(w8 + p.off_records);
-    const size_t lds_sc = scatter_cm_lds_bytes(p.TB, p.chunk);
-    static std::atomic<uint32_t> g_epoch{0};
-    uint32_t epoch = 0u;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(st, &cap);
     if (cap != hipStreamCaptureStatusNone) {
-        // inside a stream capture the kernel arguments are frozen into the graph node: a host-made epoch would already be the
-        // published one on every replay after the first (workgroups could then OR their flags into the header BEFORE workgroup 0
-        // zeroes it).  A captured call resets the header with a kernel node of its own and passes epoch 0 = "nobody resets, nobody waits".
-        // (a kernel node, not hipMemsetAsync: a captured memset node of this runtime wrote a stale pattern into the header from its
-        // second replay on -- measured; tests/test_taf_fast_gpu.py replays a captured encode three times)
         hipLaunchKernelGGL(kf_header_reset, dim3(1), dim3(256), 0, st, hdr);
-    } else {
-        epoch = g_epoch.fetch_add(1u, std::memory_order_relaxed) + 1u;
-        if (epoch == 0u) epoch = g_epoch.fetch_add(1u, std::memory_order_relaxed) + 1u; // (0 = the captured form)
+        return 0u;
     }
+    uint32_t epoch = (counter.fetch_add(1u, std::memory_order_relaxed) + 1u) | range;
+    if (epoch == 0u) epoch = (counter.fetch_add(1u, std::memory_order_relaxed) + 1u) | range; // (0 = the captured form)
+    return epoch;
+}
+
+// one instance of the chunk-major scatter: the dynamic-LDS attribute where it is needed (always for the one-workgroup-per-CU
+// form), then the launch.  tlut: the per-call value table the kernel fills on the side, or NULL (SAE / Event Count Image)
+template <bool HAS_MAP, bool EV, bool SIMPLE, int MAXB = kMaxBpw, int SAE = 0>
+void launch_scatter_cm(const FastGeom &G, const SeqTab &S, const FastPlan &p, char *w8, float *tlut, uint32_t epoch, hipStream_t st)
+{
+    const size_t lds_sc = scatter_cm_lds_bytes(p.TB, p.chunk);
+    if (MAXB > kMaxBpw || lds_sc > 64 * 1024)
+        (void)hipFuncSetAttribute((const void *)kf_scatter_cm<HAS_MAP, EV, SIMPLE, MAXB, SAE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sc);
+    hipLaunchKernelGGL((kf_scatter_cm<HAS_MAP, EV, SIMPLE, MAXB, SAE>), dim3(p.chunks), dim3(kFT), lds_sc, st, G, S, (uint32_t *)(w8 + p.off_counts),
+                       (uint32_t *)(w8 + p.off_records), (FastHeader *)w8, tlut, epoch);
+}
+
+// the chunk-major partition: ONE kernel (its first workgroup resets the header; a reset kernel in front of it inside a capture)
+template <bool HAS_MAP, bool EV = false>
+void launch_fast_cm(const FastGeom &G, const SeqTab &S, const FastPlan &p, char *w8, hipStream_t st)
+{
+    static std::atomic<uint32_t> g_epoch{0};
+    const uint32_t epoch = cm_epoch(g_epoch, 0u, (FastHeader *)w8, st);
+    float *tlut = (float *)(w8 + p.off_tlut);
     const bool simple = !HAS_MAP && G.simple != 0;
-    if (p.big && simple) {
-        (void)hipFuncSetAttribute((const void *)kf_scatter_cm<false, EV, true, kBigBpw>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sc);
-        hipLaunchKernelGGL((kf_scatter_cm<false, EV, true, kBigBpw>), dim3(p.chunks), dim3(kFT), lds_sc, st, G, S, dir, records, hdr, tlut, epoch);
-    } else if (p.big) {
-        (void)hipFuncSetAttribute((const void *)kf_scatter_cm<HAS_MAP, EV, false, kBigBpw>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sc);
-        hipLaunchKernelGGL((kf_scatter_cm<HAS_MAP, EV, false, kBigBpw>), dim3(p.chunks), dim3(kFT), lds_sc, st, G, S, dir, records, hdr, tlut, epoch);
-    } else if (simple) {
-        if (lds_sc > 64 * 1024)
-            (void)hipFuncSetAttribute((const void *)kf_scatter_cm<false, EV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sc);
-        hipLaunchKernelGGL((kf_scatter_cm<false, EV, true>), dim3(p.chunks), dim3(kFT), lds_sc, st, G, S, dir, records, hdr, tlut, epoch);
-    } else {
-        if (lds_sc > 64 * 1024)
-            (void)hipFuncSetAttribute((const void *)kf_scatter_cm<HAS_MAP, EV, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sc);
-        hipLaunchKernelGGL((kf_scatter_cm<HAS_MAP, EV, false>), dim3(p.chunks), dim3(kFT), lds_sc, st, G, S, dir, records, hdr, tlut, epoch);
-    }
-    return FRLW_OK;
+    if (p.big && simple) launch_scatter_cm<false, EV, true, kBigBpw>(G, S, p, w8, tlut, epoch, st);
+    else if (p.big) launch_scatter_cm<HAS_MAP, EV, false, kBigBpw>(G, S, p, w8, tlut, epoch, st);
+    else if (simple) launch_scatter_cm<false, EV, true>(G, S, p, w8, tlut, epoch, st);
+    else launch_scatter_cm<HAS_MAP, EV, false>(G, S, p, w8, tlut, epoch, st);
+}
+
+// the first level of a batch call: either partition, with or without coordinate maps
+template <bool EV>
+void launch_partition(const FastGeom &G, const SeqTab &S, const FastPlan &p, bool cm, char *w8, hipStream_t st)
+{
+    if (cm) { if (G.xmap) launch_fast_cm<true, EV>(G, S, p, w8, st); else launch_fast_cm<false, EV>(G, S, p, w8, st); }
+    else if (G.xmap) launch_fast<true, EV>(G, S, p, w8, st);
+    else launch_fast<false, EV>(G, S, p, w8, st);
 }
 
 // chunk-major partition or histogram partition?  frlw_tuning_t::chunk_major = 0 forces the histogram partition; otherwise the
-// chunk-major one runs wherever a consumer can hold a sequence's column of the directory in LDS (cm_fits) and nobody asked for
-// the tile walk, which wants contiguous tile lists.  Measured (us, chunk-major against histogram partition): one
+// chunk-major one runs wherever a consumer can hold a sequence's column of the directory in LDS (cm_fits).  Measured (us, chunk-major against histogram partition): one
 // GEN1 stream 32 / 42, 5 x 70 k events on 97x131 34 / 55, 3 M events at 1280x720 111 / 133, 10 M events 164 / 177, 64 GEN1
 // streams 808 / 861, Event Volume x64 736 / 787; the skewed variants give some of it back (25 % of 10 M events in one blob:
 // 298 / 287 -- the split segments of a skewed tile are only known after the split kernel, so their counting pass is a launch
@@ -3251,27 +2892,67 @@ inline bool cm_fits(const FastPlan &p, bool ev)
     return p.max_seq_chunks <= col && p.chunk <= 65535;
 }
 
-// plan + layout of one call: tries the chunk-major plan first where the knob allows it
-inline int plan_call(const frlw_tuning_t *tu, bool ev, bool tile_walk_wanted, long long n, int n_seq, int H, int W,
-                     const int64_t *seq_offsets, const int64_t *t0, uint32_t win, FastPlan &p, SeqTab &S, bool &cm)
+// The argument checks the two batch entry points share (their own -- outputs, K / bins, window counts: all FRLW_ERR_ARG -- come
+// in front of this).  t0: the per-sequence t_start / t_end array.
+int batch_args_check(const frlw_events_t *ev, const int64_t *seq_offsets, const int64_t *t0, int n_seq, const void *workspace)
 {
+    if (!ev || !seq_offsets || !t0 || !workspace) return FRLW_ERR_ARG;
+    if (n_seq < 1 || n_seq > kMaxSeq) return FRLW_ERR_ARG;
+    if (ev->layout != FRLW_LAYOUT_DAT8) return FRLW_ERR_UNSUPPORTED;
+    if ((ev->xmap == nullptr) != (ev->ymap == nullptr)) return FRLW_ERR_ARG;
+    if (!tuning_valid(ev->tuning)) return FRLW_ERR_ARG;
+    if (seq_offsets[0] < 0 || seq_offsets[n_seq] > ev->n) return FRLW_ERR_ARG;
+    if (seq_offsets[n_seq] > seq_offsets[0] && !ev->data) return FRLW_ERR_ARG;
+    return FRLW_OK;
+}
+
+// plan + layout of one batch call (tries the chunk-major plan first where the knob allows it), then what both entry points
+// ask of the result: the workspace holds it, the scatter workgroup's LDS exists
+inline int plan_call(const frlw_tuning_t *tu, bool ev, int n_seq, int H, int W, const int64_t *seq_offsets,
+                     const int64_t *t0, int64_t window_us, size_t workspace_bytes, FastPlan &p, SeqTab &S, bool &cm)
+{
+    const long long n = seq_offsets[n_seq] - seq_offsets[0];
     const int knob = tuning_knob(tu, &frlw_tuning_t::chunk_major, CM_AUTO);
     const int bpw = tuning_knob(tu, &frlw_tuning_t::batches_per_wave, 0);
-    const int dmode = [&] {
-        const int direct = tuning_knob(tu, &frlw_tuning_t::direct_bins, -1);
-        if (direct >= 0) return direct != 0 ? (int)DIRECT_FORCE : (int)DIRECT_OFF;
-        return tile_walk_wanted ? (int)DIRECT_OFF : (int)DIRECT_AUTO;
-    }();
+    const int direct = tuning_knob(tu, &frlw_tuning_t::direct_bins, -1);
+    const int dmode = direct < 0 ? (int)DIRECT_AUTO : (direct != 0 ? (int)DIRECT_FORCE : (int)DIRECT_OFF);
     cm = false;
-    if (knob != CM_OFF && !tile_walk_wanted) {
+    if (knob != CM_OFF) {
         if (!fast_plan(n, n_seq, H, W, p, dmode, bpw, true)) return FRLW_ERR_UNSUPPORTED;
-        if (!fast_layout(seq_offsets, t0, n_seq, p, S, win)) return FRLW_ERR_ARG;
+        if (!fast_layout(seq_offsets, t0, n_seq, p, S, (uint32_t)window_us)) return FRLW_ERR_ARG;
         cm = cm_fits(p, ev);
-        if (cm) return FRLW_OK;
     }
-    if (!fast_plan(n, n_seq, H, W, p, dmode, bpw, false)) return FRLW_ERR_UNSUPPORTED;
-    if (!fast_layout(seq_offsets, t0, n_seq, p, S, win)) return FRLW_ERR_ARG;
+    if (!cm) {
+        if (!fast_plan(n, n_seq, H, W, p, dmode, bpw, false)) return FRLW_ERR_UNSUPPORTED;
+        if (!fast_layout(seq_offsets, t0, n_seq, p, S, (uint32_t)window_us)) return FRLW_ERR_ARG;
+    }
+#ifdef FRLW_DEV_BUILD // the size query covers what any call lays out (one layout function: layout_offsets)
+    if (p.bytes > frlw_taf_batch_workspace_bytes(n, n_seq, H, W, window_us)) { fprintf(stderr, "taf_fast: layout above the size query\n"); abort(); }
+#endif
+    if (workspace_bytes < p.bytes) return FRLW_ERR_WORKSPACE;
+    if (scatter_lds_bytes(p.TB, p.chunk) > 160 * 1024) return FRLW_ERR_UNSUPPORTED;
     return FRLW_OK;
+}
+
+// The FastGeom fields that come from the plan and the event descriptor, as a whole-frame call of ONE window; an entry point
+// adds what is its own: windows (n_windows, wb, win, win_magic), rcp, simple / span, the stripe rows.
+inline FastGeom plan_geom(const frlw_events_t *ev, const FastPlan &p, int H, int W)
+{
+    FastGeom G = {};
+    G.data = (const uint2 *)ev->data;
+    G.xmap = ev->xmap; G.ymap = ev->ymap; G.map_w = ev->map_w; G.map_h = ev->map_h;
+    G.H = H; G.W = W; G.twl = p.twl; G.thl = p.thl; G.tiles_x = p.tiles_x; G.T = p.TB; G.bin_shift = p.bin_shift; G.bin_mask = p.direct ? 15 : 0; G.bpw = p.bpw;
+    G.chunk_ev = p.chunk; G.run = p.chunk / kFW; G.n_total = ev->n;
+    G.n_windows = 1; G.y_lo = 0; G.H_full = H;
+    return G;
+}
+
+// every sequence's t0 inside the 32-bit range of the SIMPLE decode
+inline bool t0_fits_simple(const SeqTab &S)
+{
+    for (int s = 0; s < S.n_seq; ++s)
+        if (S.t0[s] < 0 || S.t0[s] > 0xffffffffll) return false;
+    return true;
 }
 
 inline CmP cm_params(const FastPlan &p, char *w8)
@@ -3289,18 +2970,42 @@ inline CmP cm_params(const FastPlan &p, char *w8)
     return cm;
 }
 
-// second level of the chunk-major partition: q.rec2 / q.sub / q.sub_end afterwards describe one contiguous list per sub-tile
-inline void launch_split_cm(TileP &q, const FastPlan &p, const SeqTab &S, char *w8, hipStream_t st)
+// The second level, for TAF and Event Volume: fills the partition-table fields of q and brings the records sub-tile-major --
+// afterwards q.rec2 / q.sub / q.sub_end describe one contiguous list per sub-tile.  The four forms:
+//   chunk-major + direct  nothing runs here: the consumers gather their own lists (and book space in rec2[] for the long ones)
+//   chunk-major           kf_split_whole<true>, then the segment kernels for the skewed tiles it booked
+//   direct                kf_scatter's bins were the sub-tiles: its output IS the sub-tile-major list, base[] its sub[]
+//   histogram             kf_split_whole<false> (tiles, then segment counts in its spare workgroups) + kf_split_place<false>
+// The caller has set what is its own (geometry, outputs, TAF: wst / wst_flag for the chunk-major form).
+void launch_second_level(TileP &q, const FastPlan &p, const SeqTab &S, bool cm, char *w8, hipStream_t st)
 {
-    const CmP cm = cm_params(p, w8);
+    q.T = p.T; q.pairs = p.pairs; q.direct = p.direct;
+    q.hdr = (FastHeader *)w8;
+    q.rec = (const uint32_t *)(w8 + p.off_records);
     q.rec2 = (uint32_t *)(w8 + p.off_records2);
+    q.base = (const uint32_t *)(w8 + p.off_base);
     q.sub = (uint32_t *)(w8 + p.off_sub);
-    q.sub_end = (uint32_t *)(w8 + p.off_sub_end);
-    // (direct mode never comes here: its consumers gather their own lists)
-    const int seg_grid = p.max_segs < 512 ? p.max_segs : 512; // (they stride over the segments; most calls have none; two workgroups per CU)
-    hipLaunchKernelGGL(kf_split_whole<true>, dim3(p.pairs), dim3(kFT), 0, st, q, cm, S);
-    hipLaunchKernelGGL(kf_segcount_cm, dim3(seg_grid), dim3(kFT), 0, st, q, cm, S);
-    hipLaunchKernelGGL(kf_split_place<true>, dim3(seg_grid), dim3(kFT), 0, st, q, cm, S);
+    q.sub_end = nullptr;
+    q.seg0 = (const uint32_t *)(w8 + p.off_seg0);
+    q.segcnt = (uint32_t *)(w8 + p.off_segcnt);
+    q.seg_grid = p.max_segs < 2048 ? p.max_segs : 2048;
+    q.tile_max = whole_max_of(p.pairs);
+    if (cm && p.direct) return;
+    if (cm) {
+        const CmP cmq = cm_params(p, w8);
+        q.sub_end = (uint32_t *)(w8 + p.off_sub_end);
+        const int seg_grid = p.max_segs < 512 ? p.max_segs : 512; // (they stride over the segments; most calls have none; two workgroups per CU)
+        hipLaunchKernelGGL(kf_split_whole<true>, dim3(p.pairs), dim3(kFT), 0, st, q, cmq, S);
+        hipLaunchKernelGGL(kf_segcount_cm, dim3(seg_grid), dim3(kFT), 0, st, q, cmq, S);
+        hipLaunchKernelGGL(kf_split_place<true>, dim3(seg_grid), dim3(kFT), 0, st, q, cmq, S);
+    } else if (p.direct) {
+        q.rec2 = (uint32_t *)(w8 + p.off_records);
+        q.sub = (uint32_t *)(w8 + p.off_base);
+    } else {
+        const CmP none = {};
+        hipLaunchKernelGGL(kf_split_whole<false>, dim3(p.pairs + q.seg_grid), dim3(kFT), 0, st, q, none, S);
+        hipLaunchKernelGGL(kf_split_place<false>, dim3(q.seg_grid), dim3(kFT), 0, st, q, none, S);
+    }
 }
 
 // ---- one-time check of the hardware property this file rests on ------------------------------------------------------
@@ -3400,22 +3105,8 @@ size_t frlw_taf_batch_workspace_bytes(int64_t n_events, int n_seq, int H, int W,
         // can add one partly filled chunk and one partly filled slab
         const size_t chunks = (size_t)(n_events + p.chunk - 1) / p.chunk + n_seq;
         const size_t slabs = chunks / kFastSlab + n_seq + 1;
-        size_t off = kHeaderBytes;
-        off = align_up(off + chunks * p.TB * 4, 256);
-        off = align_up(off + slabs * p.TB * 4, 256);
-        off = align_up(off + (size_t)(p.pairs_b + 1) * 4, 256);
-        off = align_up(off + ((size_t)p.pairs * kFW + 1) * 4, 256);
-        off = align_up(off + (size_t)(p.pairs_b + 1) * 4, 256);
-        off = align_up(off + (2 * (size_t)(n_events / kSplitSeg) + 1) * kFW * 4, 256);
-        off = align_up(off + chunks * 4, 256);
-        off = align_up(off + (size_t)(window_us + 1) * 4, 256);
-        off = align_up(off + (size_t)(n_events > 0 ? n_events : 1) * 4, 256);
-        off = align_up(off + (size_t)(n_events > 0 ? n_events : 1) * 4, 256);
-        off = align_up(off + ((size_t)p.pairs * kFW + 1) * 4, 256);
-        off = align_up(off + (2 * (size_t)(n_events / kSplitSeg) + 1) * 4, 256);
-        off = align_up(off + (size_t)p.pairs * kFW * (FRLW_MAX_WINDOWS + 1) * 4, 256);
-        off = align_up(off + (size_t)p.pairs * 4, 256);
-        if (off > need) need = off;
+        layout_offsets(p, chunks, slabs, n_events, (size_t)window_us);
+        if (p.bytes > need) need = p.bytes;
     }
     return need;
 }
@@ -3432,54 +3123,35 @@ int taf_batch_run(int phases, const frlw_events_t *ev, const int64_t *seq_offset
                   int y_lo, int H_full, int K, int64_t window_us, int n_windows, float *state, float *view_f32, uint8_t *out_u8,
                   int flags, void *workspace, size_t workspace_bytes, frlw_stream_t stream)
 {
-    if (!ev || !seq_offsets || !t_start || !workspace || (!state && (phases & PHASE_FINISH))) return FRLW_ERR_ARG;
+    if (!state && (phases & PHASE_FINISH)) return FRLW_ERR_ARG;
     if (y_lo < 0 || H < 1 || y_lo + H > H_full) return FRLW_ERR_ARG;
     if (K < 1 || K > FRLW_MAX_BINS || n_windows < 1 || n_windows > FRLW_MAX_WINDOWS || window_us < 1) return FRLW_ERR_ARG;
-    if (n_seq < 1 || n_seq > kMaxSeq) return FRLW_ERR_ARG;
-    if (ev->layout != FRLW_LAYOUT_DAT8) return FRLW_ERR_UNSUPPORTED;
-    if ((ev->xmap == nullptr) != (ev->ymap == nullptr)) return FRLW_ERR_ARG;
-    if (!tuning_valid(ev->tuning)) return FRLW_ERR_ARG;
-    if (seq_offsets[0] < 0 || seq_offsets[n_seq] > ev->n) return FRLW_ERR_ARG;
-    if (seq_offsets[n_seq] > seq_offsets[0] && !ev->data) return FRLW_ERR_ARG;
+    {
+        const int rc = batch_args_check(ev, seq_offsets, t_start, n_seq, workspace);
+        if (rc != FRLW_OK) return rc;
+    }
     // record = r | window | cell in 32 bits
     int wb = 0, rb = 0;
     while ((1 << wb) < n_windows) ++wb;
     while ((1ll << rb) <= window_us) ++rb;
     if (kCellBits + wb + rb > 32 || (long long)n_windows * window_us >= (1ll << 32)) return FRLW_ERR_UNSUPPORTED;
-    const long long n = seq_offsets[n_seq] - seq_offsets[0];
     FastPlan p;
     SeqTab S;
     bool cm = false;
-    const bool walk_wanted = tuning_knob(ev->tuning, &frlw_tuning_t::taf_tile_walk, kTafTileWalk ? 1 : 0) != 0 &&
-                             tuning_knob(ev->tuning, &frlw_tuning_t::direct_bins, -1) <= 0;
     {
-        const int rc = plan_call(ev->tuning, false, walk_wanted, n, n_seq, H, W, seq_offsets, t_start, (uint32_t)window_us, p, S, cm);
+        const int rc = plan_call(ev->tuning, false, n_seq, H, W, seq_offsets, t_start, window_us, workspace_bytes, p, S, cm);
         if (rc != FRLW_OK) return rc;
     }
-    if (workspace_bytes < p.bytes) return FRLW_ERR_WORKSPACE;
-    if (scatter_lds_bytes(p.TB, p.chunk) > 160 * 1024) return FRLW_ERR_UNSUPPORTED;
 
-    FastGeom G;
-    G.data = (const uint2 *)ev->data;
-    G.xmap = ev->xmap; G.ymap = ev->ymap; G.map_w = ev->map_w; G.map_h = ev->map_h;
-    G.H = H; G.W = W; G.twl = p.twl; G.thl = p.thl; G.tiles_x = p.tiles_x; G.T = p.TB; G.bin_shift = p.bin_shift; G.bin_mask = p.direct ? 15 : 0; G.bpw = p.bpw;
-    G.chunk_ev = p.chunk; G.run = p.chunk / kFW; G.n_total = ev->n;
+    FastGeom G = plan_geom(ev, p, H, W);
     G.n_windows = n_windows; G.wb = wb; G.win = (uint32_t)window_us;
     G.rcp = 1.0 / ((double)(uint32_t)window_us + 1e-8); // generate_taf.py:215: t / (w + 1e-8)
     G.y_lo = y_lo; G.H_full = H_full;
-    {
-        const bool want = tuning_knob(ev->tuning, &frlw_tuning_t::taf_tile_walk, kTafTileWalk ? 1 : 0) != 0;
-        G.order_check = (want && !p.direct && p.pairs >= kFewPairs) ? 1 : 0;
-    }
     const unsigned long long magic = (1ull << 32) / (unsigned long long)window_us;
     G.win_magic = magic > 0xffffffffull ? 0xffffffffu : (uint32_t)magic;
-    {
-        bool simple = y_lo == 0 && H_full == H && window_us >= 2 &&
-                      (unsigned long long)n_windows * (unsigned long long)window_us <= 0xffffffffull;
-        for (int s = 0; s < n_seq && simple; ++s) simple = S.t0[s] >= 0 && S.t0[s] <= 0xffffffffll;
-        G.simple = simple ? 1 : 0;
-        G.span = simple ? (uint32_t)((unsigned long long)n_windows * (unsigned long long)window_us) : 0u;
-    }
+    G.simple = (y_lo == 0 && H_full == H && window_us >= 2 &&
+                (unsigned long long)n_windows * (unsigned long long)window_us <= 0xffffffffull && t0_fits_simple(S)) ? 1 : 0;
+    G.span = G.simple ? (uint32_t)((unsigned long long)n_windows * (unsigned long long)window_us) : 0u;
 
     hipStream_t st = (hipStream_t)stream;
     char *w8 = (char *)workspace;
@@ -3488,57 +3160,19 @@ int taf_batch_run(int phases, const frlw_events_t *ev, const int64_t *seq_offset
         const int ok = lds_order_ok(w8, st); // cached per device after the first call
         if (ok != FRLW_OK) return ok;
     }
-    if (phases & PHASE_PARTITION) {
-        if (cm) {
-            const int rc = ev->xmap ? launch_fast_cm<true>(G, S, p, w8, st) : launch_fast_cm<false>(G, S, p, w8, st);
-            if (rc != FRLW_OK) return rc;
-        } else if (ev->xmap) launch_fast<true>(G, S, p, w8, st);
-        else launch_fast<false>(G, S, p, w8, st);
-    }
+    if (phases & PHASE_PARTITION) launch_partition<false>(G, S, p, cm, w8, st);
     if (!(phases & PHASE_FINISH)) { HIP_TRY(hipGetLastError()); return FRLW_OK; }
-    TileP q;
-    q.H = H; q.W = W; q.twl = p.twl; q.thl = p.thl; q.tiles_x = p.tiles_x; q.T = p.T; q.K = K; q.n_windows = n_windows;
+    TileP q = {};
+    q.H = H; q.W = W; q.twl = p.twl; q.thl = p.thl; q.tiles_x = p.tiles_x; q.K = K; q.n_windows = n_windows;
     q.wb = wb; q.flip = (flags & FRLW_TAF_U8_FLIP_K) ? 1 : 0; q.win = (uint32_t)window_us; q.rcp = G.rcp;
-    q.rec = (const uint32_t *)(w8 + p.off_records);
-    q.rec2 = (uint32_t *)(w8 + p.off_records2);
-    q.base = (const uint32_t *)(w8 + p.off_base);
-    q.sub = (uint32_t *)(w8 + p.off_sub);
-    q.seg0 = (const uint32_t *)(w8 + p.off_seg0);
-    q.segcnt = (uint32_t *)(w8 + p.off_segcnt);
-    q.pairs = p.pairs;
-    q.skip_whole = 0;
-    q.first_block = 0;
-    q.seg_grid = p.max_segs < 2048 ? p.max_segs : 2048;
-    q.tile_walk = G.order_check;
-    q.tile_max = whole_max_of(p.pairs);
     q.tlut = (const float *)(w8 + p.off_tlut);
     if (!(q.leaky_thr = leaky_table(st))) return FRLW_ERR_HIP; // device-resident constant, built once per device (partition.hip)
-    q.hdr = (FastHeader *)w8;
     q.state = state; q.view_f32 = view_f32; q.out_u8 = out_u8;
-    q.direct = p.direct;
-    q.sub_end = nullptr;
-    q.wst = nullptr; q.wst_flag = nullptr;
-    if (cm && p.direct) {
-        q.rec2 = (uint32_t *)(w8 + p.off_records2); // (kf_taf_walk<.., true> books and fills its own list)
-    } else if (cm) {
-        if (tuning_knob(ev->tuning, &frlw_tuning_t::walk_window_table, 1) != 0) { // kf_split_whole<true> leaves the walk its window starts
-            q.wst = (uint32_t *)(w8 + p.off_wst);
-            q.wst_flag = (uint32_t *)(w8 + p.off_wst_flag);
-        }
-        launch_split_cm(q, p, S, w8, st);
-    } else if (p.direct) { // kf_scatter's bins were the sub-tiles: its output IS the sub-tile-major list, base[] its sub[]
-        q.rec2 = (uint32_t *)(w8 + p.off_records);
-        q.sub = (uint32_t *)(w8 + p.off_base);
-    } else {
-        const CmP none = {};
-        hipLaunchKernelGGL(kf_split_whole<false>, dim3(p.pairs + q.seg_grid), dim3(kFT), 0, st, q, none, S); // tiles, then segment counts
-        hipLaunchKernelGGL(kf_split_place<false>, dim3(q.seg_grid), dim3(kFT), 0, st, q, none, S);
+    if (cm && !p.direct && tuning_knob(ev->tuning, &frlw_tuning_t::walk_window_table, 1) != 0) { // kf_split_whole<true> leaves the walk its window starts
+        q.wst = (uint32_t *)(w8 + p.off_wst);
+        q.wst_flag = (uint32_t *)(w8 + p.off_wst_flag);
     }
-    if (q.tile_walk) { // tiles of window-sorted sequences below the skew limit: split in LDS by the kernel that consumes them
-        const int grid = (p.pairs + 7) / 8 * 8;
-        if (K == 8) hipLaunchKernelGGL((kf_taf_tile<kFW, true>), dim3(grid), dim3(kFT), 0, st, q);
-        else hipLaunchKernelGGL((kf_taf_tile<kFW, false>), dim3(grid), dim3(kFT), 0, st, q);
-    }
+    launch_second_level(q, p, S, cm, w8, st);
     const CmP cmq = cm ? cm_params(p, w8) : CmP{};
     if (cm && p.direct) { // the walk gathers its own list (no gather kernel)
         if (K == 8) hipLaunchKernelGGL((kf_taf_walk<true, true>), dim3(p.pairs * kFW), dim3(kWalkThreads), 0, st, q, cmq, S);
@@ -3590,13 +3224,12 @@ int frlw_ev_encode_batch(const frlw_events_t *ev, const int64_t *seq_offsets, co
                          int bins, int64_t window_us, float *out_f32, uint8_t *out_u8, void *workspace,
                          size_t workspace_bytes, frlw_stream_t stream)
 {
-    if (!ev || !seq_offsets || !t_end || !workspace || (!out_f32 && !out_u8)) return FRLW_ERR_ARG;
-    if (bins < 1 || bins > FRLW_MAX_BINS || window_us < 1 || n_seq < 1 || n_seq > kMaxSeq) return FRLW_ERR_ARG;
-    if (ev->layout != FRLW_LAYOUT_DAT8) return FRLW_ERR_UNSUPPORTED;
-    if ((ev->xmap == nullptr) != (ev->ymap == nullptr)) return FRLW_ERR_ARG;
-    if (!tuning_valid(ev->tuning)) return FRLW_ERR_ARG;
-    if (seq_offsets[0] < 0 || seq_offsets[n_seq] > ev->n) return FRLW_ERR_ARG;
-    if (seq_offsets[n_seq] > seq_offsets[0] && !ev->data) return FRLW_ERR_ARG;
+    if (!out_f32 && !out_u8) return FRLW_ERR_ARG;
+    if (bins < 1 || bins > FRLW_MAX_BINS || window_us < 1) return FRLW_ERR_ARG;
+    {
+        const int rc = batch_args_check(ev, seq_offsets, t_end, n_seq, workspace);
+        if (rc != FRLW_OK) return rc;
+    }
     int rb = 0; // record = (t - t_begin) | cell in 32 bits
     while ((1ll << rb) <= window_us) ++rb;
     if (kCellBits + rb > 32) return FRLW_ERR_UNSUPPORTED;
@@ -3606,28 +3239,15 @@ int frlw_ev_encode_batch(const frlw_events_t *ev, const int64_t *seq_offsets, co
     int64_t t_begin[kMaxSeq];
     for (int s = 0; s < n_seq; ++s) t_begin[s] = t_end[s] - window_us; // generate_eventvolume.py:139-141
     bool cm = false;
-    const bool walk_wanted = tuning_knob(ev->tuning, &frlw_tuning_t::taf_tile_walk, kTafTileWalk ? 1 : 0) != 0 &&
-                             tuning_knob(ev->tuning, &frlw_tuning_t::direct_bins, -1) <= 0;
     {
-        const int rc = plan_call(ev->tuning, true, walk_wanted, n, n_seq, H, W, seq_offsets, t_begin, (uint32_t)window_us, p, S, cm);
+        const int rc = plan_call(ev->tuning, true, n_seq, H, W, seq_offsets, t_begin, window_us, workspace_bytes, p, S, cm);
         if (rc != FRLW_OK) return rc;
     }
-    if (workspace_bytes < p.bytes) return FRLW_ERR_WORKSPACE;
-    if (scatter_lds_bytes(p.TB, p.chunk) > 160 * 1024) return FRLW_ERR_UNSUPPORTED;
 
-    FastGeom G;
-    G.data = (const uint2 *)ev->data;
-    G.xmap = ev->xmap; G.ymap = ev->ymap; G.map_w = ev->map_w; G.map_h = ev->map_h;
-    G.H = H; G.W = W; G.twl = p.twl; G.thl = p.thl; G.tiles_x = p.tiles_x; G.T = p.TB; G.bin_shift = p.bin_shift; G.bin_mask = p.direct ? 15 : 0; G.bpw = p.bpw;
-    G.chunk_ev = p.chunk; G.run = p.chunk / kFW; G.n_total = ev->n;
-    G.n_windows = 1; G.wb = 0; G.win = (uint32_t)window_us; G.win_magic = 0u; G.order_check = 0; G.y_lo = 0; G.H_full = H;
+    FastGeom G = plan_geom(ev, p, H, W);
+    G.win = (uint32_t)window_us;
     G.rcp = 1.0 / (double)(uint32_t)window_us; // generate_eventvolume.py:141
-    {
-        bool simple = true; // (t0 = t_end - window is negative for a label in the first `window` microseconds of a file)
-        for (int s = 0; s < n_seq && simple; ++s) simple = S.t0[s] >= 0 && S.t0[s] <= 0xffffffffll;
-        G.simple = simple ? 1 : 0;
-        G.span = 0u;
-    }
+    G.simple = t0_fits_simple(S) ? 1 : 0; // (t0 = t_end - window is negative for a label in the first `window` microseconds of a file)
 
     hipStream_t st = (hipStream_t)stream;
     char *w8 = (char *)workspace;
@@ -3636,58 +3256,14 @@ int frlw_ev_encode_batch(const frlw_events_t *ev, const int64_t *seq_offsets, co
         const int ok = lds_order_ok(w8, st); // cached per device after the first call
         if (ok != FRLW_OK) return ok;
     }
-    if (cm) {
-        const int rc = ev->xmap ? launch_fast_cm<true, true>(G, S, p, w8, st) : launch_fast_cm<false, true>(G, S, p, w8, st);
-        if (rc != FRLW_OK) return rc;
-    } else if (ev->xmap) launch_fast<true, true>(G, S, p, w8, st);
-    else launch_fast<false, true>(G, S, p, w8, st);
-    // Second-level split: kf_split_whole + kf_ev_sub by default; the tile walk (kf_ev_tile, 3.4: the split in LDS, 2.44x instead
-    // of 2.8x HBM traffic) on request -- it was the default until kf_split_whole became a one-pass kernel, which made the two-kernel
-    // form the faster one (64 x 1 M events: 985 against 1 041 us)
-    bool tile_walk = false;
-    {
-        const bool want = tuning_knob(ev->tuning, &frlw_tuning_t::taf_tile_walk, kTafTileWalk ? 1 : 0) != 0;
-        tile_walk = want && !p.direct && p.pairs >= kFewPairs;
-    }
-    TileP q;
-    memset(&q, 0, sizeof(q));
-    q.T = p.T; q.pairs = p.pairs; q.skip_whole = tile_walk ? 1 : 0;
-    q.rec = (const uint32_t *)(w8 + p.off_records);
-    q.rec2 = (uint32_t *)(w8 + p.off_records2);
-    q.base = (const uint32_t *)(w8 + p.off_base);
-    q.sub = (uint32_t *)(w8 + p.off_sub);
-    q.seg0 = (const uint32_t *)(w8 + p.off_seg0);
-    q.segcnt = (uint32_t *)(w8 + p.off_segcnt);
-    q.hdr = (FastHeader *)w8;
-    q.first_block = tile_walk ? p.pairs : 0; // with the tile walk only the segment-counting blocks have work
-    q.seg_grid = p.max_segs < 2048 ? p.max_segs : 2048;
-    q.tile_max = whole_max_of(p.pairs);
-    if (cm && p.direct) {
-        q.rec2 = (uint32_t *)(w8 + p.off_records2); // (kf_ev_sub<.., true> books and fills its own lists)
-    } else if (cm) {
-        launch_split_cm(q, p, S, w8, st);
-    } else if (p.direct) { // kf_scatter's bins were the sub-tiles: its output IS the sub-tile-major list, base[] its sub[]
-        q.rec2 = (uint32_t *)(w8 + p.off_records);
-        q.sub = (uint32_t *)(w8 + p.off_base);
-    } else {
-        const CmP none = {};
-        hipLaunchKernelGGL(kf_split_whole<false>, dim3(p.pairs + q.seg_grid - q.first_block), dim3(kFT), 0, st, q, none, S); // tiles, then segment counts
-        hipLaunchKernelGGL(kf_split_place<false>, dim3(q.seg_grid), dim3(kFT), 0, st, q, none, S);
-    }
+    launch_partition<true>(G, S, p, cm, w8, st);
+    TileP q = {}; // second level: kf_split_whole + kf_ev_sub (one wavefront per sub-tile list)
+    launch_second_level(q, p, S, cm, w8, st);
     EvTileP e;
     e.H = H; e.W = W; e.twl = p.twl; e.thl = p.thl; e.tiles_x = p.tiles_x; e.T = p.T; e.bins = bins; e.win = (uint32_t)window_us; e.rcp = G.rcp;
-    e.rec = q.rec; e.rec2 = q.rec2; e.base = q.base; e.sub = q.sub; e.sub_end = q.sub_end; e.pairs = p.pairs; e.tile_max = whole_max_of(p.pairs); e.direct = p.direct;
+    e.rec2 = q.rec2; e.base = q.base; e.sub = q.sub; e.sub_end = q.sub_end; e.pairs = p.pairs; e.direct = p.direct;
     e.tlut = (const float *)(w8 + p.off_tlut); e.hdr = (FastHeader *)w8; e.out_f32 = out_f32; e.out_u8 = out_u8;
     const int sub_grid = (p.pairs * kFW + 3) / 4;
-    if (tile_walk) {
-#ifndef FRLW_EV_NW
-#define FRLW_EV_NW 16
-#endif
-        constexpr int NW = FRLW_EV_NW, PARTS = kFW / NW;
-        const int grid = (p.pairs + 7) / 8 * 8 * PARTS;
-        if (bins <= 5) hipLaunchKernelGGL((kf_ev_tile<NW, 5>), dim3(grid), dim3(NW * kWave), 0, st, e);
-        else hipLaunchKernelGGL((kf_ev_tile<NW, kMaxK>), dim3(grid), dim3(NW * kWave), 0, st, e);
-    }
     const CmP cmq = cm ? cm_params(p, w8) : CmP{};
     bool fadd = false;
     {
@@ -3703,10 +3279,10 @@ int frlw_ev_encode_batch(const frlw_events_t *ev, const int64_t *seq_offsets, co
         if (bins <= 5) hipLaunchKernelGGL((kf_ev_fadd<5>), dim3(p.pairs * kFW), dim3(kFaddWaves * kWave), 0, st, e, cmq, S);
         else hipLaunchKernelGGL((kf_ev_fadd<kMaxK>), dim3(p.pairs * kFW), dim3(kFaddWaves * kWave), 0, st, e, cmq, S);
     } else if (cm && p.direct) { // the sub-tile wavefronts gather their own lists
-        if (bins <= 5) hipLaunchKernelGGL((kf_ev_sub<5, true>), dim3(sub_grid), dim3(4 * kWave), 0, st, e, 1, cmq, S);
-        else hipLaunchKernelGGL((kf_ev_sub<kMaxK, true>), dim3(sub_grid), dim3(4 * kWave), 0, st, e, 1, cmq, S);
-    } else if (bins <= 5) hipLaunchKernelGGL((kf_ev_sub<5, false>), dim3(sub_grid), dim3(4 * kWave), 0, st, e, tile_walk ? 0 : 1, cmq, S);
-    else hipLaunchKernelGGL((kf_ev_sub<kMaxK, false>), dim3(sub_grid), dim3(4 * kWave), 0, st, e, tile_walk ? 0 : 1, cmq, S);
+        if (bins <= 5) hipLaunchKernelGGL((kf_ev_sub<5, true>), dim3(sub_grid), dim3(4 * kWave), 0, st, e, cmq, S);
+        else hipLaunchKernelGGL((kf_ev_sub<kMaxK, true>), dim3(sub_grid), dim3(4 * kWave), 0, st, e, cmq, S);
+    } else if (bins <= 5) hipLaunchKernelGGL((kf_ev_sub<5, false>), dim3(sub_grid), dim3(4 * kWave), 0, st, e, cmq, S);
+    else hipLaunchKernelGGL((kf_ev_sub<kMaxK, false>), dim3(sub_grid), dim3(4 * kWave), 0, st, e, cmq, S);
     HIP_TRY(hipGetLastError());
     return FRLW_OK;
 }
@@ -3761,37 +3337,21 @@ int sae_fast_try(const frlw_events_t *ev, int H, int W, const float *lam, int n_
     SeqTab S;
     if (!sae_fast_plan(n, H, W, now - window_us, p, S)) return 1;
     if (workspace_bytes < p.bytes) return 1; // (frlw_encoder_workspace_bytes covers p.bytes: only a caller that sized the workspace itself gets here)
-    FastGeom G;
-    G.data = (const uint2 *)ev->data;
-    G.xmap = ev->xmap; G.ymap = ev->ymap; G.map_w = ev->map_w; G.map_h = ev->map_h;
-    G.H = H; G.W = W; G.twl = p.twl; G.thl = p.thl; G.tiles_x = p.tiles_x; G.T = p.TB; G.bin_shift = p.bin_shift; G.bin_mask = 15; G.bpw = p.bpw;
-    G.chunk_ev = p.chunk; G.run = p.chunk / kFW; G.n_total = n;
-    G.n_windows = 1; G.wb = 0; G.win = 0xffffffffu; G.win_magic = 0u; G.order_check = 0; G.y_lo = 0; G.H_full = H;
-    G.rcp = 0.0;
-    G.simple = (S.t0[0] >= 0 && S.t0[0] <= 0xffffffffll) ? 1 : 0;
-    G.span = 0u;
+    FastGeom G = plan_geom(ev, p, H, W); // (the plan is a direct-mode one: sub-tile bins)
+    G.win = 0xffffffffu;
+    G.simple = t0_fits_simple(S) ? 1 : 0;
     char *w8 = (char *)workspace;
     FastHeader *hdr = (FastHeader *)w8;
-    uint32_t *dir = (uint32_t *)(w8 + p.off_counts);
-    uint32_t *records = (uint32_t *)(w8 + p.off_records);
-    const size_t lds_sc = scatter_cm_lds_bytes(p.TB, p.chunk);
     (void)hipGetLastError();
-    static std::atomic<uint32_t> g_epoch_sae{0x40000000u}; // (its own range: never equal to a TAF / Event Volume call's epoch of the same process ... within 2^30 calls)
-    uint32_t epoch = 0u;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(st, &cap);
-    if (cap != hipStreamCaptureStatusNone) hipLaunchKernelGGL(kf_header_reset, dim3(1), dim3(256), 0, st, hdr);
-    else epoch = g_epoch_sae.fetch_add(1u, std::memory_order_relaxed) | 0x40000000u;
-#define SAE_SCATTER(MAP, SIMPLE_, MODE) do { \
-        if (lds_sc > 64 * 1024) (void)hipFuncSetAttribute((const void *)kf_scatter_cm<MAP, true, SIMPLE_, kMaxBpw, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sc); \
-        hipLaunchKernelGGL((kf_scatter_cm<MAP, true, SIMPLE_, kMaxBpw, MODE>), dim3(p.chunks), dim3(kFT), lds_sc, st, G, S, dir, records, hdr, (float *)nullptr, epoch); } while (0)
+    static std::atomic<uint32_t> g_epoch_sae{0};
+    const uint32_t epoch = cm_epoch(g_epoch_sae, 0x40000000u, hdr, st);
+    float *const no_table = nullptr;
     if (eci) { // (t0 = -1 is outside the SIMPLE decode's range: the general form keeps every event)
-        if (ev->xmap) SAE_SCATTER(true, false, 2);
-        else SAE_SCATTER(false, false, 2);
-    } else if (ev->xmap) SAE_SCATTER(true, false, 1);
-    else if (G.simple) SAE_SCATTER(false, true, 1);
-    else SAE_SCATTER(false, false, 1);
-#undef SAE_SCATTER
+        if (ev->xmap) launch_scatter_cm<true, true, false, kMaxBpw, 2>(G, S, p, w8, no_table, epoch, st);
+        else launch_scatter_cm<false, true, false, kMaxBpw, 2>(G, S, p, w8, no_table, epoch, st);
+    } else if (ev->xmap) launch_scatter_cm<true, true, false, kMaxBpw, 1>(G, S, p, w8, no_table, epoch, st);
+    else if (G.simple) launch_scatter_cm<false, true, true, kMaxBpw, 1>(G, S, p, w8, no_table, epoch, st);
+    else launch_scatter_cm<false, true, false, kMaxBpw, 1>(G, S, p, w8, no_table, epoch, st);
     SaeFastP q;
     q.H = H; q.W = W; q.twl = p.twl; q.thl = p.thl; q.tiles_x = p.tiles_x; q.T = p.T; q.n_lamda = n_lamda;
     for (int l = 0; l < (eci ? 21 : n_lamda); ++l) q.lam[l] = lam[l];

@@ -70,9 +70,8 @@ typedef struct frlw_tuning {
     int32_t staged_scatter;   /* 0 / 1: records leave the partition through an LDS staging area */
     int32_t quarter_below;    /* frames with at most this many wavefronts run every tile as four quarter workgroups */
     int32_t no_value_table;   /* 1: TAF DAT8 computes the f64 division per event instead of the per-call table */
-    int32_t taf_tile_walk;    /* frlw_taf_encode_batch / frlw_ev_encode_batch: 1 = tiles are split in LDS by the kernel that walks
-                               * them (kf_taf_tile / kf_ev_tile: less HBM traffic, measured slower), 0 = split pass + sub-tile
-                               * kernel (the default) */
+    int32_t taf_tile_walk;    /* RETIRED (the slot keeps the struct's layout): once selected an opt-in second-level split that was
+                               * measured slower and has been removed.  0 / 1 / -1 are accepted and ignored. */
     int32_t direct_bins;      /* frlw_taf_encode_batch / frlw_ev_encode_batch: 1 = the partition's bins are the 256-cell sub-tiles
                                * wherever the frame allows it (at most 64 tiles: the 304x240 class) -- no second-level split pass
                                * at all; 0 = always tile bins + split pass; default: sub-tile bins for calls with fewer than 512
@@ -80,7 +79,7 @@ typedef struct frlw_tuning {
     int32_t chunk_major;      /* frlw_taf_encode_batch / frlw_ev_encode_batch: 1 = the chunk-major partition (no histogram pass: the
                                * scatter writes every chunk sorted by bin where it stands plus a directory row, the consumers
                                * gather -- the default wherever a sequence has at most 4096 chunks), 0 = histogram + scans +
-                               * bin-major scatter (the only form for longer sequences and for the tile walk) */
+                               * bin-major scatter (the only form for longer sequences) */
     int32_t ev_lds_float_atomics; /* frlw_ev_encode_batch, direct mode of the chunk-major partition: 1 = one wavefront per sub-tile
                                * sums its list with LDS float atomics in stream order (kf_ev_fadd: short latency chain, 3 x the
                                * cycles per record -- the default up to 3 M events per call), 0 = the ticket-sort kernel */

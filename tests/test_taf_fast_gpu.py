@@ -304,17 +304,19 @@ def test_failed_lane_order_selftest_disables_the_fast_path():
     assert p.returncode == 0 and "forced-failure ok" in p.stdout, p.stdout[-2000:] + p.stderr[-4000:]
 
 
-# ---- the tile walk (kf_taf_tile, frlw_tuning_t::taf_tile_walk = 1): same bits as the default split + sub-tile kernels ----
+# ---- the two partitions (chunk-major, the default; histogram, frlw_tuning_t::chunk_major = 0): same bits -----------------------
 def _batch(seed, B, n, H, W, span, hotspot=False):
     recs = [synth.to_dat8(synth.synth_events(seed + j, n if j != 2 else n // 40, W, H, span, hotspot=hotspot)) for j in range(B)]
     return recs, np.concatenate([[0], np.cumsum([len(r) for r in recs])])
 
 
 @pytest.mark.parametrize("K,n_win,win", [(8, 8, 10_000), (4, 3, 977), (5, 16, 5_000)])
-def test_tile_walk_equals_default_path(er, monkeypatch, K, n_win, win):
-    """A batch with >= 256 (sequence, tile) pairs, one sparse sequence, one sequence with an empty window and one whose
-    stream is NOT time-sorted (the tile walk needs window-sorted lists: kf_scatter flags it and it takes the default
-    kernels inside the same call), plus a hot spot that pushes tiles over the segment limit."""
+def test_histogram_partition_equals_default_path(er, monkeypatch, K, n_win, win):
+    """A batch with >= 256 (sequence, tile) pairs, one sparse sequence, one sequence with an empty window, one whose
+    stream is NOT time-sorted and one whose time runs backwards (their sub-tile lists are not window-sorted: the walk filters
+    them per window), plus a hot spot that pushes tiles over the segment limit -- through the default chunk-major partition
+    and through the independent histogram partition (kf_hist, scans, kf_scatter, kf_split_whole<false>).  The retired
+    frlw_tuning_t::taf_tile_walk slot is accepted and ignored: same bits as the default."""
     from frlw_evd_amd import _lib
     H, W, B = 240, 304, 8  # 40 tiles per sequence -> 320 pairs
     recs, _ = _batch(4400 + K, B, 260_000, H, W, n_win * win, hotspot=True)
@@ -325,26 +327,27 @@ def test_tile_walk_equals_default_path(er, monkeypatch, K, n_win, win):
     offs = np.concatenate([[0], np.cumsum([len(r) for r in recs])])
     dat = to_dev(np.concatenate(recs))
     init = torch.from_numpy(np.random.default_rng(3).uniform(-50, 0, (B, H, W, 2, K)).astype(np.float32)).cuda()
-    sa, sb = init.clone(), init.clone()
+    sa, sb, sc = init.clone(), init.clone(), init.clone()
     ua, va = er.encode_taf_batch(dat, offs, (H, W), sa, 0, win, n_win, K, want_view=True)
-    monkeypatch.setattr(er, "TUNING", _lib.FrlwTuning(taf_tile_walk=1))
+    monkeypatch.setattr(er, "TUNING", _lib.FrlwTuning(chunk_major=0))
     ub, vb = er.encode_taf_batch(dat, offs, (H, W), sb, 0, win, n_win, K, want_view=True)
     assert not torch.equal(sa, init)
     assert torch.equal(sa, sb), "state"
     assert torch.equal(va, vb), "view"
     assert torch.equal(ua, ub), "uint8"
+    monkeypatch.setattr(er, "TUNING", _lib.FrlwTuning(taf_tile_walk=1))  # retired: the call succeeds and takes the default path
+    uc, vc = er.encode_taf_batch(dat, offs, (H, W), sc, 0, win, n_win, K, want_view=True)
+    assert torch.equal(sa, sc) and torch.equal(va, vc) and torch.equal(ua, uc), "taf_tile_walk = 1 changes the result"
 
 
-def test_tile_walk_mpx_golden(er, monkeypatch, golden_dir):
-    """The reference's own 10 M-event 1280x720 state (sha256 golden) through the tile walk."""
+def test_mpx_golden_through_the_batch_entry_point(er, golden_dir):
+    """The reference's own 10 M-event 1280x720 state (sha256 golden) through frlw_taf_encode_batch's default path."""
     import hashlib
     import os
-    from frlw_evd_amd import _lib
     g = np.load(os.path.join(golden_dir, "mpx_taf_native.npz"))
     H, W, K = 720, 1280, 8
     rec = synth.to_dat8(synth.synth_events(1003, 10_000_000, W, H, 80_000))
     st = torch.full((1, H, W, 2, K), -6000.0, device="cuda")
-    monkeypatch.setattr(er, "TUNING", _lib.FrlwTuning(taf_tile_walk=1))
     er.encode_taf_batch(to_dev(rec), [0, len(rec)], (H, W), st, 0, 10_000, 8, K)
     assert hashlib.sha256(host(st[0]).tobytes()).hexdigest() == str(g["state_sha"])
 

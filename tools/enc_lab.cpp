@@ -4,7 +4,7 @@
 // also compares the outputs byte for byte (the first one is the reference build, e.g. the last parity-green commit).
 //
 //   hipcc -O2 -std=c++17 -I include tools/enc_lab.cpp -o build/enc_lab -ldl
-//   build/enc_lab frlw-evd_amd/csrc/libfrlw_evd.so [build/libfrlw_base.so] [--cfg mpx,mpx_hot,gen1,gen1x64,e2e64,ev1,evb64] [--reps 20] [--tile-walk]
+//   build/enc_lab frlw-evd_amd/csrc/libfrlw_evd.so [build/libfrlw_base.so] [--cfg mpx,mpx_hot,gen1,gen1x64,e2e64,ev1,evb64] [--reps 20]
 //   rocprofv3 --kernel-trace --stats -- build/enc_lab <lib> --cfg mpx          (per-kernel breakdown of exactly that encode)
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -234,7 +234,6 @@ int main(int argc, char **argv)
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--cfg") && i + 1 < argc) only = argv[++i];
         else if (!strcmp(argv[i], "--reps") && i + 1 < argc) reps = atoi(argv[++i]);
-        else if (!strcmp(argv[i], "--tile-walk")) { g_tuning.taf_tile_walk = 1; g_use_tuning = true; } // TAF through kf_taf_tile
         else if (!strcmp(argv[i], "--bpw") && i + 1 < argc) { g_tuning.batches_per_wave = atoi(argv[++i]); g_use_tuning = true; } // larger partition chunks
         else if (!strcmp(argv[i], "--fadd")) { g_tuning.ev_lds_float_atomics = 1; g_use_tuning = true; } // Event Volume, direct mode: LDS float atomics
         else if (!strcmp(argv[i], "--no-fadd")) { g_tuning.ev_lds_float_atomics = 0; g_use_tuning = true; } // ... the ticket-sort kernel

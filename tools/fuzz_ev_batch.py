@@ -2,7 +2,7 @@
 """Randomised differential test of the batched Event Volume path (frlw_ev_encode_batch, csrc/taf_fast.hip) against the
 general path (frlw_ev_encode, one call per sequence), which the test-suite pins to the oracle: the f32 volume and its uint8
 form must agree bit for bit.  Random batches (1-64 label windows, empty ones included; few and many (sequence, tile) pairs:
-segment split + kf_ev_sub vs the tile walk), frame shapes, bins, window lengths, own t_end per sequence, skew (hot spots,
+segment split vs whole-tile split in front of kf_ev_sub), frame shapes, bins, window lengths, own t_end per sequence, skew (hot spots,
 single hot pixels), shuffled streams, events in front of the window (dropped) and exactly on its end.
 
     python tools/fuzz_ev_batch.py [cases] [seed]
@@ -55,9 +55,8 @@ def main():
             recs.append(synth.to_dat8(ev))
             ends.append(t_end)
         offs = np.concatenate([[0], np.cumsum([len(r) for r in recs])])
-        # every third case: the opt-in tile walk (kf_ev_tile); the others: the partition mode at random
-        er.TUNING = (_lib.FrlwTuning(taf_tile_walk=1) if case % 3 == 2 else
-                     [_lib.FrlwTuning(chunk_major=int(rng.integers(-1, 2)), ev_lds_float_atomics=int(rng.integers(-1, 2))),
+        # the partition mode at random
+        er.TUNING = ([_lib.FrlwTuning(chunk_major=int(rng.integers(-1, 2)), ev_lds_float_atomics=int(rng.integers(-1, 2))),
                       _lib.FrlwTuning(direct_bins=1, chunk_major=int(rng.integers(-1, 2)), ev_lds_float_atomics=int(rng.integers(-1, 2))),
                       _lib.FrlwTuning(direct_bins=0, chunk_major=int(rng.integers(-1, 2)))][int(rng.integers(0, 3))])
         try:

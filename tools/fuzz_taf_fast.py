@@ -34,14 +34,13 @@ def main():
         W = int(rng.integers(8, 700)) if rng.random() < 0.7 else int(rng.integers(600, 1300))
         if B >= 16:
             H, W = min(H, 120), min(W, 160)
-        # every third case through the tile walk (kf_taf_tile; takes effect from 256 (sequence, tile) pairs on: make some)
-        tile_walk = case % 3 == 2
-        if tile_walk and rng.random() < 0.7:
+        # every third case: a good chance of 256 or more (sequence, tile) pairs (whole-tile split instead of the segment kernels)
+        if case % 3 == 2 and rng.random() < 0.7:
             B, H, W = int(rng.choice([8, 16, 33])), int(rng.integers(150, 260)), int(rng.integers(250, 420))
-        # the others: the partition mode at random (library's choice / sub-tile bins forced where the frame allows / tile bins)
+        # the partition mode at random (library's choice / sub-tile bins forced where the frame allows / tile bins)
         cmaj = int(rng.integers(-1, 2))  # the partition: library's choice / histogram + scans / chunk-major
-        er.TUNING = _lib.FrlwTuning(taf_tile_walk=1) if tile_walk else [_lib.FrlwTuning(chunk_major=cmaj), _lib.FrlwTuning(direct_bins=1, chunk_major=cmaj), _lib.FrlwTuning(direct_bins=0, chunk_major=cmaj)][int(rng.integers(0, 3))]
-        if not tile_walk and rng.random() < 0.15:  # the one-workgroup-per-CU scatter (big chunks), which only 6 M-event calls take by themselves
+        er.TUNING = [_lib.FrlwTuning(chunk_major=cmaj), _lib.FrlwTuning(direct_bins=1, chunk_major=cmaj), _lib.FrlwTuning(direct_bins=0, chunk_major=cmaj)][int(rng.integers(0, 3))]
+        if rng.random() < 0.15:  # the one-workgroup-per-CU scatter (big chunks), which only 6 M-event calls take by themselves
             er.TUNING = _lib.FrlwTuning(chunk_major=1, direct_bins=0, batches_per_wave=int(rng.choice([9, 12, 20])))
         K = int(rng.choice([8, 8, 8, 5, 4, 1, 7]))
         n_win = int(rng.choice([1, 2, 3, 8, 8, 13, 64]))
@@ -87,7 +86,7 @@ def main():
             uj, vj = er.encode_taf_dat(dev(recs[s]), (H, W), sj, starts[s], win, n_win, K, want_view=True, flip_k=flip, fast=False)
             if not (torch.equal(sj, st[s]) and torch.equal(vj, view[s]) and torch.equal(uj, u8[s])):
                 bad += 1
-                print(f"MISMATCH case {case} seq {s}: tile_walk={tile_walk} B={B} H={H} W={W} K={K} n_win={n_win} win={win} n={len(recs[s])} "
+                print(f"MISMATCH case {case} seq {s}: tuning={er.TUNING and (er.TUNING.chunk_major, er.TUNING.direct_bins, er.TUNING.batches_per_wave)} B={B} H={H} W={W} K={K} n_win={n_win} win={win} n={len(recs[s])} "
                       f"state={bool(torch.equal(sj, st[s]))} view={bool(torch.equal(vj, view[s]))} u8={bool(torch.equal(uj, u8[s]))}")
                 break
     print(f"{cases} cases ({skipped} outside the fast path's shapes), {bad} mismatches")
