@@ -81,7 +81,7 @@ def build_dev(force: bool = False) -> str:
 
 def build(force: bool = False, verbose: bool = False) -> str:
     if force or needs_build() or os.environ.get("FRLW_LIB_OUT"):
-        extra = os.environ.get("FRLW_EXTRA_HIPCC_FLAGS", "").split()  # experiments only (e.g. -DCONV_BK_BIG=32)
+        extra = os.environ.get("FRLW_EXTRA_HIPCC_FLAGS", "").split()  # experiments only (e.g. -DSK_ROWS=4)
         out = os.environ.get("FRLW_LIB_OUT") or LIB  # experiments only: build a variant beside the product
         _compile_and_link(out, extra, "product", force, verbose)
     return LIB

@@ -91,16 +91,7 @@ __device__ __forceinline__ void conv_split8(const f32x4 &q0, const f32x4 &q1, u3
     }
 }
 
-#ifndef CONV_BK_BIG
-#define CONV_BK_BIG 16
-#endif
-#ifndef CONV_BK_SMALL
-#define CONV_BK_SMALL 16
-#endif
-constexpr int kSplitBK = 16; // granularity the split-K heuristics count k-tiles in
-#ifndef CONV_F32_PIPE
-#define CONV_F32_PIPE 1 // 0: the float32-MFMA loop without the pipelined iteration seam (A/B in tools/conv_lab.hip)
-#endif
+constexpr int BK = 16; // the k-tile of every kernel here: four 16-byte quads per gathered row, one bf16 k-step; split-K counts k-tiles in it
 
 // BatchNorm statistics in the train forward's epilogues (ConvArgs::stats).  Sums of squares of raw float32 values lose what
 // little is left of the variance when a channel's mean dominates its spread (every square is rounded to 2^-24 of mean^2).
@@ -152,18 +143,17 @@ __device__ __forceinline__ float4 conv_load16(__amdgpu_buffer_rsrc_t r, uint32_t
 // BM x BN output tile, 4 wavefronts arranged WROWS x WCOLS, each owning TM x TN MFMA tiles of 32 x 32.
 // UT ("uniform taps"): Cin % BK == 0, so a k-tile lies inside one filter tap and the tap changes for the whole
 // workgroup at once: the gather offsets are recomputed only then, a k-tile costs one add per load.
-template <int BM, int BN, int WROWS, int WCOLS, int BK, bool UT, int D, int P, bool SK>
+template <int BM, int BN, int WROWS, int WCOLS, bool UT, int P, bool SK>
 __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a);
 
-template <int BM, int BN, int WROWS, int WCOLS, int BK, bool UT, int D = 2, int P = 0>
-__global__ __launch_bounds__(64 * WROWS * WCOLS) void k_conv_mfma(ConvArgs a)
+template <int BM, int BN, int WROWS, int WCOLS, bool UT, int P = 0>
+__global__ __launch_bounds__(256) void k_conv_mfma(ConvArgs a)
 {
-    conv_mfma_body<BM, BN, WROWS, WCOLS, BK, UT, D, P, false>(a);
+    conv_mfma_body<BM, BN, WROWS, WCOLS, UT, P, false>(a);
 }
 
 // the 64 x 64 tile with the split-K reduction inside the kernel (see the epilogue): its last-arriving workgroup keeps 16 partial
 // rows in registers, and the launches that use it want five workgroups per CU -- five wavefronts per SIMD, at most 96 registers
-template <int BK>
 #ifndef SK_OCC
 #define SK_OCC 5
 #endif
@@ -172,32 +162,30 @@ template <int BK>
 #endif
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SK_OCC, 8))) void k_conv_mfma_sk(ConvArgs a)
 {
-    conv_mfma_body<64, 64, 2, 2, BK, true, 2, 0, true>(a);
+    conv_mfma_body<64, 64, 2, 2, true, 0, true>(a);
 }
 
-template <int BM, int BN, int WROWS, int WCOLS, int BK, bool UT, int D, int P, bool SK>
+template <int BM, int BN, int WROWS, int WCOLS, bool UT, int P, bool SK>
 __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a)
 {
-    constexpr int NT = 64 * WROWS * WCOLS; // four wavefronts (eight for the 128 x 256 tile)
+    static_assert(WROWS * WCOLS == 4, "every tile is computed by four wavefronts");
+    constexpr int NT = 256;
     constexpr int TM = BM / (32 * WROWS), TN = BN / (32 * WCOLS);
-    constexpr int KQ = BK / 4;        // float4 per A row of the k-tile
+    constexpr int KQ = 4;             // float4 per A row of the k-tile
     constexpr int RPP = NT / KQ;      // A rows staged per pass of the NT threads
     // Both operand tiles arrive by LDS-DMA (buffer_load ... lds: no registers, no ds_write), so their LDS images are
     // lane-linear: weights [BK][BN], gathered rows [BM][BK] with the four 16-byte quads of a row XOR-swizzled by
     // (row >> 2) & 3 on the SOURCE side, which makes the ds_read_b128 fragment reads conflict-free.
-    static_assert(BK == 16 || (BK == 32 && P == 1), "the A image is four quads per row (eight with the bf16 k-steps: two per k-tile)");
-    constexpr int KS = BK / 16;       // bf16 k-steps per k-tile (P == 1)
     constexpr int LDB = BN;
     constexpr int A_F4 = BM * BK / 4 / NT;    // float4 loads per thread for the A tile
     constexpr int B_F4 = (BN * BK / 4 + NT - 1) / NT;
     constexpr int EPLD = 36;                          // row pitch of the epilogue staging (16-byte aligned rows)
-    // LDS rings.  The gathered operand streams from HBM / the far L2: its tile t + D is requested while tile t is
-    // computed (D + 1 slots).  The weights are L2-resident and shared by every workgroup: D - 1 tiles ahead (D slots).
-    // D = 2 where many workgroups share a CU (they hide each other's latency and LDS is what limits their number);
-    // D = 4 for launches that leave a workgroup alone on its CU: its k-tile then costs latency / D, not latency / 2.
-    constexpr int NA = D + 1, NB = D;
+    // LDS rings.  The gathered operand streams from HBM / the far L2: its tile t + 2 is requested while tile t is
+    // computed (three slots).  The weights are L2-resident and shared by every workgroup: one tile ahead (two slots).
+    // Deeper rings (prefetch distance 3 and 4) were measured and gained nothing: a workgroup that is alone on its CU is bound by
+    // the issue cost of its own DMA and fragment instructions, not by prefetch distance, and LDS is what limits the others per CU.
+    constexpr int NA = 3, NB = 2;
     static_assert((BM * BK / 4) % NT == 0, "whole passes over the gathered tile");
-    static_assert(D == 2 || (BN * BK / 4) % NT == 0, "deeper rings count on every wavefront issuing the same DMAs");
     constexpr int kTileFloats = BK * (NA * BM + NB * LDB);
     constexpr int kEpiFloats = (NT / 64) * 32 * EPLD; // one 32 x 32 MFMA tile per wavefront
     __shared__ __attribute__((aligned(16))) float smem[kTileFloats > kEpiFloats ? kTileFloats : kEpiFloats];
@@ -217,9 +205,9 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a)
     const __amdgpu_buffer_rsrc_t rx = conv_rsrc(a.x, a.x_bytes), rw = conv_rsrc(a.w, a.w_bytes);
 
     // ---- A staging: thread -> A_F4 rows m, one float4 of 4 consecutive k
-    // the quad this lane FETCHES; it lands in slot tid % KQ of its row (row tid / KQ): slot ^ f(row), f = (row >> 2) & 3 for
-    // 64-byte rows, (row >> 1) & 7 for 128-byte rows -- the 16 lanes of a ds_read_b128 pass then cover all 64 banks
-    const int a_k4 = (KQ == 4 ? ((tid & 3) ^ ((tid >> 4) & 3)) : ((tid & 7) ^ ((tid >> 4) & 7))) * 4;
+    // the quad this lane FETCHES; it lands in slot tid % KQ of its row (row tid / KQ): slot ^ f(row), f = (row >> 2) & 3
+    // -- the 16 lanes of a ds_read_b128 pass then cover all 64 banks
+    const int a_k4 = ((tid & 3) ^ ((tid >> 4) & 3)) * 4;
     int a_iy0[A_F4], a_ix0[A_F4];
     uint32_t a_base[A_F4]; // byte offset of the row's image (+ channel offset); kOob for rows past M
 #pragma unroll
@@ -252,7 +240,7 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a)
     for (int i = 0; i < B_F4; ++i) {
         const int e = tid + NT * i;
         if (P == 1) { // 16-byte record e of the tile image [h][hi | lo][BN]
-            const int hp = e / BN, n = e - hp * BN; // hp = 4 * (k-step of the tile) + 2 h + part
+            const int hp = e / BN, n = e - hp * BN; // hp = 2 h + part
             b_off[i] = (hp < BK / 4 && n0 + n < a.Npad) ? (uint32_t)((((long long)kt0 * (BK / 4) + hp) * a.Npad + n0 + n) * 16) : kOob;
         } else {
             const int kr = e / BN4, n4 = (e - kr * BN4) * 4;
@@ -319,10 +307,10 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
-    // Issue order inside an iteration: weights of tile t + D - 1 first, gathered rows of tile t + D last.  The newest
-    // instructions behind the weights of tile t + 1 are then A(t + 2) and D - 2 whole (B, A) pairs: "all but my newest
-    // kInFlight DMA instructions have landed" (a counted vmcnt) is exactly "tile t + 1 is complete".
-    constexpr int kInFlight = A_F4 + (D - 2) * (A_F4 + B_F4);
+    // Issue order inside an iteration: weights of tile t + 1 first, gathered rows of tile t + 2 last.  The newest
+    // instructions behind the weights of tile t + 1 are then the rows of tile t + 2: "all but my newest kInFlight DMA
+    // instructions have landed" (a counted vmcnt) is exactly "tile t + 1 is complete".
+    constexpr int kInFlight = A_F4;
     auto wait_next_tile = [&](bool steady) { // wave-uniform
         if (steady) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kInFlight) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -330,28 +318,28 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a)
     PROBE_PH(0);
     load_a(kt0, 0);
 #pragma unroll
-    for (int i = 0; i < D - 1; ++i) { // the issue order of the iterations -(D - 1) .. -1
+    for (int i = 0; i < 1; ++i) { // iteration -1 in the issue order of the loops below: tiles 0 (weights) and 1 (rows)
         if (i < nk) load_b(i);
         if (i + 1 < nk) load_a(kt0 + i + 1, i + 1);
     }
     PROBE_PH(1);
-    wait_next_tile(nk >= D);
+    wait_next_tile(nk >= 2);
     __builtin_amdgcn_s_barrier(); // raw barrier: __syncthreads() would drain the DMA of the tiles in flight
     PROBE_PH(2);
     // MFMA k-step (j, t), j = 0..1, t = 0..3: lane half h supplies k = 8 j + 4 h + t -- any pairing of the tile's 16 k
     // works as long as both operands use it; this one lets a lane take its four A values of a j from ONE 16-byte read.
     static_assert(TM <= 2 && (TN <= 2 || (P == 1 && TN <= 4)), "fragment reads are written out for at most two tiles per direction (four columns of tiles with the bf16 k-steps)");
-    const int fh = lane >> 5, fsw = KQ == 4 ? ((lane & 31) >> 2) & 3 : ((lane & 31) >> 1) & 7;
+    const int fh = lane >> 5, fsw = ((lane & 31) >> 2) & 3;
     const int fm = wr * TM * 32 + (lane & 31), fn = wc * TN * 32 + (lane & 31);
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float *)smem;
     // byte addresses in ring slot 0: A quad (2 j + h) ^ swizzle of row fm (second tile: + 32 rows = 2048 B), B row 4 h
-    uint32_t a_lds[2 * KS]; // quad 4 s + 2 j + h of row fm, swizzled
+    uint32_t a_lds[2]; // quad 2 j + h of row fm, swizzled
 #pragma unroll
-    for (int q = 0; q < 2 * KS; ++q) a_lds[q] = lds0 + (uint32_t)(fm * BK + ((2 * q + fh) ^ fsw) * 4) * 4;
+    for (int q = 0; q < 2; ++q) a_lds[q] = lds0 + (uint32_t)(fm * BK + ((2 * q + fh) ^ fsw) * 4) * 4;
     const uint32_t b_lds = lds0 + (uint32_t)(NA * BK * BM + 4 * fh * LDB + fn) * 4;
     const uint32_t b3_lds = lds0 + (uint32_t)(NA * BK * BM) * 4 + (uint32_t)(2 * fh * BN + fn) * 16; // prec 1: record (h, hi, column fn)
     int buf = 0, bufb = 0; // ring slots of tile kt: A (kt % NA), B (kt % NB)
-    if constexpr (P == 1 && BK == 16 && TM * TN == 1) { // (wider wavefront tiles lose a wavefront per SIMD to the second register set: measured slower)
+    if constexpr (P == 1 && TM * TN == 1) { // (wider wavefront tiles lose a wavefront per SIMD to the second register set: measured slower)
         // bf16 k-steps, software-pipelined: with the matrix work of a k-tile down to TM * TN * 3 MFMAs of 32 cycles, a wavefront's
         // chain "fragment reads -> wait -> split -> MFMAs -> barrier" is what a thin layer's workgroup spends its time on (one
         // or two workgroups per CU, nobody to hide it).  The fragments of tile t + 1 are therefore requested right after the
@@ -385,8 +373,8 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a)
         };
         auto iteration = [&](auto pc, int kt) {
             constexpr int p = decltype(pc)::value;
-            if (kt + D - 1 < nk) load_b(bufb == 0 ? NB - 1 : bufb - 1);
-            if (kt + D < nk) load_a(kt0 + kt + D, buf == 0 ? NA - 1 : buf - 1);
+            if (kt + 1 < nk) load_b(bufb == 0 ? NB - 1 : bufb - 1);
+            if (kt + 2 < nk) load_a(kt0 + kt + 2, buf == 0 ? NA - 1 : buf - 1);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // the fragments of tile kt (set p) are in registers
 #pragma unroll
             for (int i = 0; i < TM; ++i) { asm volatile("" : "+v"(fa[p][0][i])); asm volatile("" : "+v"(fa[p][1][i])); }
@@ -395,7 +383,7 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a)
             u32x4 ah[TM], al[TM];
 #pragma unroll
             for (int i = 0; i < TM; ++i) conv_split8(fa[p][0][i], fa[p][1][i], ah[i], al[i]);
-            wait_next_tile(kt + D < nk);            // tile kt + 1 has landed (this wavefront's pieces) ...
+            wait_next_tile(kt + 2 < nk);            // tile kt + 1 has landed (this wavefront's pieces) ...
             __builtin_amdgcn_s_barrier();           // ... everybody's have, and everybody has tile kt in registers
             buf = buf == NA - 1 ? 0 : buf + 1;
             bufb = bufb == NB - 1 ? 0 : bufb + 1;
@@ -417,7 +405,7 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a)
         }
         if (kt < nk) iteration(ConvIC<0>{}, kt);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    } else if constexpr (P == 0 && BK == 16 && CONV_F32_PIPE && TM * TN == 1) { // (wider wavefront tiles: within +-1 %)
+    } else if constexpr (P == 0 && TM * TN == 1) { // (wider wavefront tiles: within +-1 %)
         // float32 MFMA, the iteration's seam pipelined: after the last fragment read of tile t has been issued (k-step 6 requests
         // the B row of k-step 7) the wavefront drains its LDS reads, passes the barrier that publishes tile t + 1, requests the
         // first fragments of tile t + 1 -- and only then issues the MFMAs of k-steps 6 and 7, which it has in registers.  The
@@ -462,8 +450,8 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a)
         };
         auto iteration = [&](auto pc, int kt) {
             constexpr int p = decltype(pc)::value;
-            if (kt + D - 1 < nk) load_b(bufb == 0 ? NB - 1 : bufb - 1);
-            if (kt + D < nk) load_a(kt0 + kt + D, buf == 0 ? NA - 1 : buf - 1);
+            if (kt + 1 < nk) load_b(bufb == 0 ? NB - 1 : bufb - 1);
+            if (kt + 2 < nk) load_a(kt0 + kt + 2, buf == 0 ? NA - 1 : buf - 1);
             const int sb = bufb;
             step(pc, ConvIC<0>{}, sb);
             step(pc, ConvIC<1>{}, sb);
@@ -473,7 +461,7 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a)
             step(pc, ConvIC<5>{}, sb);
             read_b(pc, ConvIC<7>{}, sb);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // every fragment of tile kt is in registers
-            wait_next_tile(kt + D < nk);                        // tile kt + 1 has landed (this wavefront's pieces) ...
+            wait_next_tile(kt + 2 < nk);                        // tile kt + 1 has landed (this wavefront's pieces) ...
             __builtin_amdgcn_s_barrier();                       // ... everybody's have, and everybody is done reading tile kt
             buf = buf == NA - 1 ? 0 : buf + 1;
             bufb = bufb == NB - 1 ? 0 : bufb + 1;
@@ -499,67 +487,63 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     } else
     for (int kt = 0; kt < nk; ++kt) {
-        if (kt + D - 1 < nk) load_b(bufb == 0 ? NB - 1 : bufb - 1);          // (kt + D - 1) % NB: read last in iteration kt - 1
-        if (kt + D < nk) load_a(kt0 + kt + D, buf == 0 ? NA - 1 : buf - 1);  // (kt + D) % NA: likewise
+        const int ahead = kt + 2; // the tile whose gathered rows this iteration requests; the weights run one tile behind it
+        if (ahead - 1 < nk) load_b(bufb == 0 ? NB - 1 : bufb - 1);          // (kt + 1) % NB: read last in iteration kt - 1
+        if (ahead < nk) load_a(kt0 + kt + 2, buf == 0 ? NA - 1 : buf - 1);  // (kt + 2) % NA: likewise
         // Fragment reads run ahead of the MFMAs that consume them (B one k-step, A one j).  They are issued as asm
         // statements with hand-counted lgkmcnt waits: the compiler puts `s_waitcnt vmcnt(0)` in front of every LDS read
         // it can see while an LDS-DMA is in flight (it cannot tell that the DMA writes another ring slot), which would
         // drain the prefetch.  LDS returns in order, so "all but the newest N reads" is exactly lgkmcnt(N); the empty asm
         // statements after a wait make the consuming MFMAs depend on it.
-        f32x4 fa[2 * KS][TM];
+        f32x4 fa[2][TM];
         const uint32_t a_slot = (uint32_t)buf * (BM * BK * 4);
-        auto read_a = [&](auto jc) { // quad pair index q = 2 s + j
+        auto read_a = [&](auto jc) { // the lane's quad of j
             constexpr int q = decltype(jc)::value;
             asm volatile("ds_read_b128 %0, %1" : "=v"(fa[q][0]) : "v"(a_lds[q] + a_slot));
             if (TM > 1) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fa[q][TM - 1]) : "v"(a_lds[q] + a_slot), "n"(32 * BK * 4));
         };
         if constexpr (P == 1) {
-            // a bf16 k-step = 16 k: the lane's eight gathered values (two quads) and its hi / lo weight records; KS per k-tile
-            u32x4 bh[KS][TN], bl[KS][TN];
+            // the k-tile is one bf16 k-step of 16 k: the lane's eight gathered values (two quads) and its hi / lo weight records
+            u32x4 bh[TN], bl[TN];
             const uint32_t b_addr = b3_lds + (uint32_t)bufb * (BK * LDB * 4);
             // (explicit captures: with [&] clang rejects the asm operands inside this generic lambda -- "reference to local variable
             // declared in enclosing function" -- and with them it warns that they are not needed)
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wunused-lambda-capture"
-            auto read_b3 = [&bh, &bl, b_addr](auto sc, auto jc) {
-                constexpr int st = decltype(sc)::value, jn = decltype(jc)::value;
-                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bh[st][jn]) : "v"(b_addr), "n"(st * 4 * BN * 16 + jn * 512));
-                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bl[st][jn]) : "v"(b_addr), "n"(st * 4 * BN * 16 + BN * 16 + jn * 512));
+            auto read_b3 = [&bh, &bl, b_addr](auto jc) {
+                constexpr int jn = decltype(jc)::value;
+                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bh[jn]) : "v"(b_addr), "n"(jn * 512));
+                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bl[jn]) : "v"(b_addr), "n"(BN * 16 + jn * 512));
             };
 #pragma clang diagnostic pop
-            auto read_step = [&](auto sc) {
-                constexpr int st = decltype(sc)::value;
-                read_a(ConvIC<2 * st>{});
-                read_a(ConvIC<2 * st + 1>{});
-                read_b3(sc, ConvIC<0>{});
-                if constexpr (TN > 1) read_b3(sc, ConvIC<1>{});
-                if constexpr (TN > 2) read_b3(sc, ConvIC<2>{});
-                if constexpr (TN > 3) read_b3(sc, ConvIC<3>{});
+            auto read_step = [&]() {
+                read_a(ConvIC<0>{});
+                read_a(ConvIC<1>{});
+                read_b3(ConvIC<0>{});
+                if constexpr (TN > 1) read_b3(ConvIC<1>{});
+                if constexpr (TN > 2) read_b3(ConvIC<2>{});
+                if constexpr (TN > 3) read_b3(ConvIC<3>{});
             };
-            auto mma_step = [&](auto sc) {
-                constexpr int st = decltype(sc)::value;
-                constexpr int later = (KS - 1 - st) * (2 * TM + 2 * TN); // reads of the later k-steps still in flight
-                asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(later) : "memory");
+            auto mma_step = [&]() {
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
-                for (int i = 0; i < TM; ++i) { asm volatile("" : "+v"(fa[2 * st][i])); asm volatile("" : "+v"(fa[2 * st + 1][i])); }
+                for (int i = 0; i < TM; ++i) { asm volatile("" : "+v"(fa[0][i])); asm volatile("" : "+v"(fa[1][i])); }
 #pragma unroll
-                for (int jn = 0; jn < TN; ++jn) { asm volatile("" : "+v"(bh[st][jn])); asm volatile("" : "+v"(bl[st][jn])); }
+                for (int jn = 0; jn < TN; ++jn) { asm volatile("" : "+v"(bh[jn])); asm volatile("" : "+v"(bl[jn])); }
                 u32x4 ah[TM], al[TM];
 #pragma unroll
-                for (int i = 0; i < TM; ++i) conv_split8(fa[2 * st][i], fa[2 * st + 1][i], ah[i], al[i]);
+                for (int i = 0; i < TM; ++i) conv_split8(fa[0][i], fa[1][i], ah[i], al[i]);
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int jn = 0; jn < TN; ++jn) { // the small terms first
-                        acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, al[i]), __builtin_bit_cast(bf16x8, bh[st][jn]), acc[i][jn], 0, 0, 0);
-                        acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah[i]), __builtin_bit_cast(bf16x8, bl[st][jn]), acc[i][jn], 0, 0, 0);
-                        acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah[i]), __builtin_bit_cast(bf16x8, bh[st][jn]), acc[i][jn], 0, 0, 0);
+                        acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, al[i]), __builtin_bit_cast(bf16x8, bh[jn]), acc[i][jn], 0, 0, 0);
+                        acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah[i]), __builtin_bit_cast(bf16x8, bl[jn]), acc[i][jn], 0, 0, 0);
+                        acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah[i]), __builtin_bit_cast(bf16x8, bh[jn]), acc[i][jn], 0, 0, 0);
                     }
             };
-            read_step(ConvIC<0>{});
-            if (KS > 1) read_step(ConvIC<KS - 1>{});
-            mma_step(ConvIC<0>{});
-            if (KS > 1) mma_step(ConvIC<KS - 1>{});
+            read_step();
+            mma_step();
         } else {
             float fb[2][TN];
             const uint32_t b_addr = b_lds + (uint32_t)bufb * (BK * LDB * 4);
@@ -603,7 +587,7 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a)
             step(ConvIC<6>{});
             step(ConvIC<7>{});
         }
-        wait_next_tile(kt + D < nk);            // tile kt + 1 has landed (this wavefront's pieces) ...
+        wait_next_tile(kt + 2 < nk);            // tile kt + 1 has landed (this wavefront's pieces) ...
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();           // ... everybody's have, and everybody is done reading tile kt
         buf = buf == NA - 1 ? 0 : buf + 1;
@@ -901,196 +885,6 @@ __device__ __forceinline__ void conv_mfma_body(const ConvArgs &a)
     }
 }
 
-#ifdef FRLW_DEV_BUILD // lab-only (tools/conv_lab.hip, FRLW_CONV_THIN16=1): measured in round 3, no net gain -- DESIGN.md section 4
-// ---- the thin-layer variant: 64 x 32 output tile, four wavefronts of 32 x 16 on v_mfma_f32_16x16x4_f32 -------------------
-// A layer of M x N outputs is M * N / 1024 wavefronts with the 32 x 32 MFMA (one accumulator tile per wavefront at least):
-// the detector's 16 x 20 and 8 x 10 levels give 1.25-2.5 wavefronts per SIMD, so the matrix pipes idle on quantisation and
-// there is nobody to hide a workgroup's prologue, barriers and epilogue.  The 16 x 16 x 4 instruction (same FLOP per cycle,
-// 40-cycle dependent latency) lets a wavefront own 32 x 16: twice the wavefronts for the same layer, 8 workgroups per CU.
-// Staging, ring, counted waits: as k_conv_mfma.  Fragments: lane l = (m = l & 15, kk = l >> 4) supplies A[row m][k] and
-// B[k][col m] with k = 4 kk + t in k-step t (the instruction sums over the four lane groups, so a k-step covers
-// k = t, 4 + t, 8 + t, 12 + t: any partition of the tile's 16 k works as long as both operands use it) -- the lane's four A
-// values are ONE 16-byte read.  LDS images (both arrive by DMA, lane-linear, so the layout is chosen on the SOURCE side):
-// row r of the gathered tile holds quad q in slot q ^ h((r >> 2) & 3), h = {0, 2, 3, 1}: the four 16-lane groups of a
-// ds_read_b128 then touch 16 distinct bank quads; row k of the weight tile has its two 16-column halves swapped when
-// (k >> 2) is odd, so the 32 lanes of a ds_read_b32 pass (kk = 0, 1 or 2, 3) hit 32 distinct banks.
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-template <bool UT>
-__global__ __launch_bounds__(256) void k_conv_mfma16(ConvArgs a)
-{
-    constexpr int BM = 64, BN = 32, BK = 16, D = 2;
-    constexpr int KQ = BK / 4, RPP = 256 / KQ, LDB = BN;
-    constexpr int A_F4 = BM * BK / 4 / 256; // 1
-    constexpr int NA = D + 1, NB = D;
-    constexpr int kTileFloats = BK * (NA * BM + NB * LDB);
-    __shared__ __attribute__((aligned(16))) float smem[kTileFloats];
-    float (*As)[BM][BK] = (float (*)[BM][BK])smem;
-    float (*Bs)[BK][LDB] = (float (*)[BK][LDB])(smem + NA * BK * BM);
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int wr = wv >> 1, wc = wv & 1;
-    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-    const __amdgpu_buffer_rsrc_t rx = conv_rsrc(a.x, a.x_bytes), rw = conv_rsrc(a.w, a.w_bytes);
-    const auto h4 = [](int g) { return g == 0 ? 0 : (g == 1 ? 2 : (g == 2 ? 3 : 1)); }; // h = {0, 2, 3, 1}
-
-    // ---- A staging: thread -> one row m, one float4 of 4 consecutive k (the quad that lands in slot tid & 3 of its row)
-    const int a_k4 = ((tid & 3) ^ h4((tid >> 4) & 3)) * 4;
-    int a_iy0, a_ix0;
-    uint32_t a_base;
-    {
-        const int m = m0 + tid / KQ;
-        const int mm = m < a.M ? m : 0;
-        const int b = mm / (a.Ho * a.Wo), pix = mm - b * (a.Ho * a.Wo);
-        const int oy = pix / a.Wo, ox = pix - oy * a.Wo;
-        a_iy0 = oy * a.stride - a.pad;
-        a_ix0 = ox * a.stride - a.pad;
-        a_base = m < a.M ? (uint32_t)(((long long)b * a.x_bs + a.x_co + (a.group_n ? (n0 / a.group_n) * a.Cin : 0)) * 4) : kOob;
-    }
-    const int kw = a.kw ? a.kw : a.k;
-    const int x_cs4 = a.x_cs * 4;
-    auto gather_off = [&](int ky, int kx) -> uint32_t {
-        int iy = a_iy0 + ky, ix = a_ix0 + kx;
-        bool ok = a_base != kOob;
-        if (a.tstride == 2) { ok = ok && !((iy | ix) & 1); iy >>= 1; ix >>= 1; }
-        ok = ok && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-        return ok ? a_base + (uint32_t)((iy * a.W + ix) * x_cs4) : kOob;
-    };
-    // ---- B staging: the first two wavefronts, one float4 each: LDS position (row kr, columns n4 .. n4 + 3) receives the
-    // weights of columns n4 ^ 16 when (kr >> 2) is odd
-    const int nk_all = (a.K + BK - 1) / BK;
-    const int kt0 = (int)((long long)nk_all * blockIdx.z / a.splits), kt1 = (int)((long long)nk_all * (blockIdx.z + 1) / a.splits);
-    const int nk = kt1 - kt0;
-    uint32_t b_off;
-    {
-        const int kr = tid / (BN / 4), n4 = ((tid % (BN / 4)) * 4) ^ (((kr >> 2) & 1) * 16);
-        b_off = (tid < BN * BK / 4 && n0 + n4 < a.Npad) ? (uint32_t)((((long long)kt0 * BK + kr) * a.Npad + n0 + n4) * 4) : kOob;
-    }
-    int s_ci, s_ky, s_kx;
-    uint32_t a_pix = kOob;
-    {
-        const int k = kt0 * BK + (UT ? 0 : a_k4);
-        const int tap = k / a.Cin;
-        s_ci = k - tap * a.Cin;
-        s_ky = tap / kw;
-        s_kx = tap - s_ky * kw;
-    }
-    if (UT) a_pix = gather_off(s_ky, s_kx);
-    auto load_a = [&](int kt, int nbuf) {
-        if (UT) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (__attribute__((address_space(3))) void *)(&As[nbuf][0][0] + wv * 64 * 4), 16,
-                                                     (int)(a_pix + (uint32_t)(s_ci + a_k4) * 4), 0, 0, 0);
-            s_ci += BK;
-            if (s_ci == a.Cin) {
-                s_ci = 0;
-                if (++s_kx == kw) { s_kx = 0; ++s_ky; }
-                a_pix = gather_off(s_ky, s_kx);
-            }
-        } else {
-            const bool in_k = kt * BK + a_k4 < a.K;
-            const uint32_t o = gather_off(s_ky, s_kx);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (__attribute__((address_space(3))) void *)(&As[nbuf][0][0] + wv * 64 * 4), 16,
-                                                     (int)(in_k ? o + (uint32_t)s_ci * 4 : kOob), 0, 0, 0);
-            s_ci += BK;
-            while (s_ci >= a.Cin) { s_ci -= a.Cin; if (++s_kx == kw) { s_kx = 0; ++s_ky; } }
-        }
-    };
-    auto load_b = [&](int nbuf) {
-        if (wv < 2) // wave-uniform: 128 float4 = two wave-instructions
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (__attribute__((address_space(3))) void *)(&Bs[nbuf][0][0] + wv * 64 * 4), 16, (int)b_off, 0, 0, 0);
-        b_off += (uint32_t)(BK * 4) * (uint32_t)a.Npad;
-    };
-
-    f32x4v acc[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[i][r] = 0.0f;
-
-    // issue order per iteration: weights of tile t + 1, then rows of tile t + 2 (as k_conv_mfma with D = 2): "all but my
-    // newest one DMA instruction has landed" = "tile t + 1 is complete" for wavefronts 0 and 1 as well as 2 and 3 (which
-    // issue no weight DMA: their newest instruction is the same row load)
-    auto wait_next_tile = [&](bool steady) {
-        if (steady) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    };
-    load_a(kt0, 0);
-    if (0 < nk) load_b(0);
-    if (1 < nk) load_a(kt0 + 1, 1);
-    wait_next_tile(nk >= D);
-    __builtin_amdgcn_s_barrier();
-    const int fm = lane & 15, fkk = lane >> 4;
-    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float *)smem;
-    // byte addresses in ring slot 0: A row (32 wr + 16 i + fm), slot fkk ^ h(fm >> 2); B row 4 fkk (+ t), column half wc ^ (fkk & 1)
-    const uint32_t a_lds = lds0 + (uint32_t)((32 * wr + fm) * BK + ((fkk ^ h4((fm >> 2) & 3)) * 4)) * 4;
-    const uint32_t b_lds = lds0 + (uint32_t)(NA * BK * BM + 4 * fkk * LDB + 16 * (wc ^ (fkk & 1)) + fm) * 4;
-    int buf = 0, bufb = 0;
-    for (int kt = 0; kt < nk; ++kt) {
-        if (kt + D - 1 < nk) load_b(bufb == 0 ? NB - 1 : bufb - 1);
-        if (kt + D < nk) load_a(kt0 + kt + D, buf == 0 ? NA - 1 : buf - 1);
-        f32x4 fa0, fa1;
-        float fb0, fb1, fb2, fb3;
-        const uint32_t a_addr = a_lds + (uint32_t)buf * (BM * BK * 4), b_addr = b_lds + (uint32_t)bufb * (BK * LDB * 4);
-        // (asm reads with a hand-counted wait: the compiler would put s_waitcnt vmcnt(0) in front of LDS reads it can see
-        // while an LDS-DMA is in flight and drain the prefetch)
-        asm volatile("ds_read_b128 %0, %1" : "=v"(fa0) : "v"(a_addr));
-        asm volatile("ds_read_b128 %0, %1 offset:1024" : "=v"(fa1) : "v"(a_addr)); // + 16 rows
-        asm volatile("ds_read_b32 %0, %1" : "=v"(fb0) : "v"(b_addr));
-        asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(fb1) : "v"(b_addr), "n"(1 * LDB * 4));
-        asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(fb2) : "v"(b_addr), "n"(2 * LDB * 4));
-        asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(fb3) : "v"(b_addr), "n"(3 * LDB * 4));
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        asm volatile("" : "+v"(fa0), "+v"(fa1), "+v"(fb0), "+v"(fb1), "+v"(fb2), "+v"(fb3));
-        acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa0[0], fb0, acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa1[0], fb0, acc[1], 0, 0, 0);
-        acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa0[1], fb1, acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa1[1], fb1, acc[1], 0, 0, 0);
-        acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa0[2], fb2, acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa1[2], fb2, acc[1], 0, 0, 0);
-        acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa0[3], fb3, acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa1[3], fb3, acc[1], 0, 0, 0);
-        wait_next_tile(kt + D < nk);
-        __builtin_amdgcn_s_barrier();
-        buf = buf == NA - 1 ? 0 : buf + 1;
-        bufb = bufb == NB - 1 ? 0 : bufb + 1;
-    }
-
-    // ---- epilogue: C/D layout of the 16 x 16 MFMA: col = lane & 15, row = 4 * (lane >> 4) + r
-    const int n = n0 + 16 * wc + fm;
-    const int howo = a.Ho * a.Wo;
-    if (a.splits > 1) {
-        float *dst = a.partial + (long long)blockIdx.z * a.M * a.Npad;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int m = m0 + 32 * wr + 16 * i + 4 * fkk + r;
-                if (m < a.M && n < a.Npad) dst[(long long)m * a.Npad + n] = acc[i][r];
-            }
-        return;
-    }
-    if (n >= a.Cout) return;
-    const float bias = a.bias ? a.bias[n] : 0.0f;
-    const int act = (a.act == ACT_SIGMOID && n < a.sig_from) ? ACT_NONE : a.act;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int mrow0 = m0 + 32 * wr + 16 * i + 4 * fkk;
-        const int b0 = mrow0 / howo, pix0 = mrow0 - b0 * howo;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            if (mrow0 + r < a.M) {
-                int b = b0, pix = pix0 + r;
-                while (pix >= howo) { pix -= howo; ++b; }
-                float v = act_apply(acc[i][r] + bias, act);
-                if (a.res) v = v + a.res[(long long)b * a.r_bs + (long long)pix * a.r_cs + a.r_co + n];
-                long long yo = (long long)pix * a.y_cs;
-                if (a.y_rp) { const int oy = pix / a.Wo; yo = (long long)oy * a.y_rp + (long long)(pix - oy * a.Wo) * a.y_cs; }
-                a.y[(long long)b * a.y_bs + yo + a.y_co + n] = v;
-            }
-        }
-    }
-}
-
-#endif // FRLW_DEV_BUILD
-
 // y = act(sum over splits of partial + bias) [+ res].  VEC: four consecutive channels per thread (16-byte loads of every
 // split's partial row, one 16-byte store); the partial sums are added in split order, as the scalar form does.
 template <bool VEC>
@@ -1167,34 +961,25 @@ __global__ __launch_bounds__(256) void k_conv_split_operand(const float *w, int 
     }
 }
 
-template <int BM, int BN, int WROWS, int WCOLS, int BK, int D = 2>
+template <int BM, int BN, int WROWS, int WCOLS>
 inline void launch_conv_tile(const ConvArgs &c, dim3 grid, hipStream_t s)
 {
-    const dim3 block(64 * WROWS * WCOLS);
     if (c.prec == 1) {
-#ifdef FRLW_DEV_BUILD // lab: k-tiles of 32 (two bf16 k-steps per barrier) -- measured, no net gain: DESIGN.md section 4
-        static const long long bk32 = dev_knob("FRLW_CONV_BK32", 0ll); // bit 0: 64 x 64 tiles, bit 1: 64 x 128, bit 2: 128 x 128, bit 3: others
-        const int bit = BM == 64 ? (BN == 64 ? 1 : 2) : (BN == 128 ? 4 : 8);
-        if ((bk32 & bit) && c.Cin % 32 == 0) {
-            hipLaunchKernelGGL((k_conv_mfma<BM, BN, WROWS, WCOLS, 32, true, D, 1>), grid, block, 0, s, c);
-            return;
-        }
-#endif
-        if (c.Cin % BK == 0) hipLaunchKernelGGL((k_conv_mfma<BM, BN, WROWS, WCOLS, BK, true, D, 1>), grid, block, 0, s, c);
-        else hipLaunchKernelGGL((k_conv_mfma<BM, BN, WROWS, WCOLS, BK, false, D, 1>), grid, block, 0, s, c);
+        if (c.Cin % BK == 0) hipLaunchKernelGGL((k_conv_mfma<BM, BN, WROWS, WCOLS, true, 1>), grid, dim3(256), 0, s, c);
+        else hipLaunchKernelGGL((k_conv_mfma<BM, BN, WROWS, WCOLS, false, 1>), grid, dim3(256), 0, s, c);
         return;
     }
-    if (c.Cin % BK == 0) hipLaunchKernelGGL((k_conv_mfma<BM, BN, WROWS, WCOLS, BK, true, D>), grid, block, 0, s, c);
-    else hipLaunchKernelGGL((k_conv_mfma<BM, BN, WROWS, WCOLS, BK, false, D>), grid, block, 0, s, c);
+    if (c.Cin % BK == 0) hipLaunchKernelGGL((k_conv_mfma<BM, BN, WROWS, WCOLS, true>), grid, dim3(256), 0, s, c);
+    else hipLaunchKernelGGL((k_conv_mfma<BM, BN, WROWS, WCOLS, false>), grid, dim3(256), 0, s, c);
 }
 
-// tiles that exist with the bf16 k-steps only
+// a tile that exists with the bf16 k-steps only (launch_conv_tile would instantiate its float32 form, whose fragment reads are
+// not written for four columns of tiles).  One user: the 128 x 128 tile of four wavefronts side by side in M.
 template <int BM, int BN, int WROWS, int WCOLS>
 inline void launch_conv_tile_p1(const ConvArgs &c, dim3 grid, hipStream_t s)
 {
-    const dim3 block(64 * WROWS * WCOLS);
-    if (c.Cin % 16 == 0) hipLaunchKernelGGL((k_conv_mfma<BM, BN, WROWS, WCOLS, 16, true, 2, 1>), grid, block, 0, s, c);
-    else hipLaunchKernelGGL((k_conv_mfma<BM, BN, WROWS, WCOLS, 16, false, 2, 1>), grid, block, 0, s, c);
+    if (c.Cin % BK == 0) hipLaunchKernelGGL((k_conv_mfma<BM, BN, WROWS, WCOLS, true, 1>), grid, dim3(256), 0, s, c);
+    else hipLaunchKernelGGL((k_conv_mfma<BM, BN, WROWS, WCOLS, false, 1>), grid, dim3(256), 0, s, c);
 }
 
 // Tile choice and split-K for one convolution; `scratch` (scratch_floats floats, may be NULL) holds split-K partials.
@@ -1224,7 +1009,7 @@ inline bool launch_conv(ConvArgs &c, float *scratch, long long scratch_floats, h
     }
     if (x_bytes > kMaxViewBytes || (long long)c.K * c.Npad * 4 > kMaxViewBytes) return false;
     c.x_bytes = (uint32_t)x_bytes;
-    if (c.Cin % 16) conv_count(FRLW_CONV_PATH_GATHERED); // (every tile takes k-tiles of 16: uniform taps need Cin % 16 == 0)
+    if (c.Cin % BK) conv_count(FRLW_CONV_PATH_GATHERED); // (uniform taps need Cin % BK == 0)
     if (c.y_rp) conv_count(FRLW_CONV_PATH_PARITY);
     c.w_bytes = (uint32_t)((long long)(c.prec == 1 ? (c.K + 15) / 16 * 16 : c.K) * c.Npad * 4);
     c.splits = 1;
@@ -1240,20 +1025,11 @@ inline bool launch_conv(ConvArgs &c, float *scratch, long long scratch_floats, h
     static const long long split_target = dev_knob("FRLW_CONV_SPLIT_TARGET", 1280ll);
     static const long long big_min = dev_knob("FRLW_CONV_BIG_MIN", 1200ll);
     static const long long wide_min = dev_knob("FRLW_CONV_WIDE_MIN", 1200ll);
-    static const long long t256_min = dev_knob("FRLW_CONV_T256_MIN", 100000ll);
     static const long long row4_min = dev_knob("FRLW_CONV_ROW4_MIN", 600ll);
-    (void)t256_min;
-#ifdef FRLW_DEV_BUILD
-    if (c.prec == 1 && c.Npad >= 256 && (long long)((c.M + 127) / 128) * ((c.Npad + 255) / 256) >= t256_min) {
-        // lab: 128 x 256 on eight wavefronts (half the L2 requests per FLOP of the 128 x 128 tile): 264 us against 204 on the
-        // 40960 x 256 x 2304 layer -- the requests were not the limit, the issue slots of the SIMDs were
-        launch_conv_tile_p1<128, 256, 2, 4>(c, dim3((c.M + 127) / 128, (c.Npad + 255) / 256), s);
-    } else
-#endif
     if (c.Npad <= 32) { // small N (prediction convs, the stem's data gradient)
         grant_stats(128);
         conv_count(FRLW_CONV_PATH_128X32);
-        launch_conv_tile<128, 32, 4, 1, 16>(c, dim3((c.M + 127) / 128, 1), s);
+        launch_conv_tile<128, 32, 4, 1>(c, dim3((c.M + 127) / 128, 1), s);
     } else if (c.prec == 1 && c.Npad >= 128 && big >= row4_min && c.K >= 512) {
         // bf16 k-steps: the four wavefronts side by side in M, each 32 rows x 128 columns -- a wavefront splits its gathered
         // values (24 VALU instructions per k-step) once for FOUR column tiles; with 2 x 2 the split cost as much issue time as the MFMAs
@@ -1263,20 +1039,15 @@ inline bool launch_conv(ConvArgs &c, float *scratch, long long scratch_floats, h
     } else if (big >= big_min && c.Npad >= 128) {
         grant_stats(128);
         conv_count(FRLW_CONV_PATH_128X128_2X2);
-        launch_conv_tile<128, 128, 2, 2, CONV_BK_BIG>(c, dim3((c.M + 127) / 128, (c.Npad + 127) / 128), s);
+        launch_conv_tile<128, 128, 2, 2>(c, dim3((c.M + 127) / 128, (c.Npad + 127) / 128), s);
     } else if (c.Npad >= 128 && (long long)((c.M + 63) / 64) * ((c.Npad + 127) / 128) >= wide_min) {
         // 64 x 128: half the im2col gathers per output of the 64 x 64 tile, still > 4 workgroups per CU
         grant_stats(64);
         conv_count(FRLW_CONV_PATH_64X128);
-        launch_conv_tile<64, 128, 2, 2, 16>(c, dim3((c.M + 63) / 64, (c.Npad + 127) / 128), s);
+        launch_conv_tile<64, 128, 2, 2>(c, dim3((c.M + 63) / 64, (c.Npad + 127) / 128), s);
     } else {
-        static const long long w2 = dev_knob("FRLW_CONV_W2", 0ll); // bf16 k-steps, two wavefronts of 32 x 64 (bit 0) / 32 x 128 (bit 1) per workgroup
-        static const long long ring4 = dev_knob("FRLW_CONV_RING4", 0ll), ring3 = dev_knob("FRLW_CONV_RING3", 0ll);
-        const bool w2n128 = c.prec == 1 && (w2 & 2) && c.Npad >= 128, w2n64 = c.prec == 1 && (w2 & 1) && !w2n128;
-        (void)ring4; (void)ring3; (void)w2n64;
-        const int bn = w2n128 ? 128 : 64;
-        const long long wgs = (long long)((c.M + 63) / 64) * ((c.Npad + bn - 1) / bn);
-        const int nk = (c.K + kSplitBK - 1) / kSplitBK;
+        const long long wgs = (long long)((c.M + 63) / 64) * ((c.Npad + 63) / 64);
+        const int nk = (c.K + BK - 1) / BK;
         // small feature maps leave most CUs idle: split the contraction over blockIdx.z
         // (contractions shorter than 1024 gained nothing from splitting while the reduction was a launch of its own; with the
         // reduction inside the kernel -- sk_counters -- those of 512 and more do: detector forward 3.833 -> 3.782 ms, same box.
@@ -1290,36 +1061,18 @@ inline bool launch_conv(ConvArgs &c, float *scratch, long long scratch_floats, h
             if (sp > nk / split_min_per) sp = (int)(nk / split_min_per);
             if (sp > 1 && (long long)sp * c.M * c.Npad <= scratch_floats) { c.splits = sp; c.partial = scratch; }
         }
-        // (a deeper ring, D = 4, for launches that leave a workgroup alone on its CU was measured: no gain -- such
-        // workgroups are bound by the issue cost of their own DMA and fragment instructions, not by prefetch distance)
-#ifdef FRLW_DEV_BUILD
-        static const long long thin16 = dev_knob("FRLW_CONV_THIN16", 0ll); // lab: 1 = the 64 x 32 / 16x16x4 variant, no split-K
-        if (thin16 && c.group_n == 0) {
-            c.splits = 1; c.partial = nullptr; c.stats = nullptr; c.stats_rows = 0;
-            if (c.Cin % 16 == 0) hipLaunchKernelGGL((k_conv_mfma16<true>), dim3((c.M + 63) / 64, (c.Npad + 31) / 32, 1), dim3(256), 0, s, c);
-            else hipLaunchKernelGGL((k_conv_mfma16<false>), dim3((c.M + 63) / 64, (c.Npad + 31) / 32, 1), dim3(256), 0, s, c);
-            return true;
-        }
-#endif
         grant_stats(64);
         const bool vec = ((c.Cout | c.Npad | c.y_cs | c.y_co | c.r_cs | c.r_co | c.y_rp) & 3) == 0 && (c.y_bs & 3) == 0 && (c.r_bs & 3) == 0;
         // the reduction inside the kernel (SK): float32 operand, uniform taps, vector rows, a counter per tile -- else k_splitk_reduce
-        if (c.splits > 1 && sk_counters && vec && c.prec == 0 && c.Cin % CONV_BK_SMALL == 0 &&
+        if (c.splits > 1 && sk_counters && vec && c.prec == 0 && c.Cin % BK == 0 &&
             (long long)((c.M + 63) / 64) * ((c.Npad + 63) / 64) <= 1024) {
             c.sk_counters = sk_counters;
             if (stats_ok && !c.bias && c.act == ACT_NONE && !c.res) { c.stats = stats_req; c.stats_rows = (c.M + 63) / 64; } // the last arriver has the whole tile
             conv_count(c.stats ? FRLW_CONV_PATH_SPLIT_INKERNEL_STATS : FRLW_CONV_PATH_SPLIT_INKERNEL);
-            hipLaunchKernelGGL((k_conv_mfma_sk<CONV_BK_SMALL>), dim3((c.M + 63) / 64, (c.Npad + 63) / 64, c.splits), dim3(256), 0, s, c);
+            hipLaunchKernelGGL(k_conv_mfma_sk, dim3((c.M + 63) / 64, (c.Npad + 63) / 64, c.splits), dim3(256), 0, s, c);
             return true;
         }
-#ifdef FRLW_DEV_BUILD // lab variants, all measured without a net gain: two-wavefront workgroups, deeper rings
-        if (w2n128) launch_conv_tile_p1<64, 128, 2, 1>(c, dim3((c.M + 63) / 64, (c.Npad + 127) / 128, c.splits), s);
-        else if (w2n64) launch_conv_tile_p1<64, 64, 2, 1>(c, dim3((c.M + 63) / 64, (c.Npad + 63) / 64, c.splits), s);
-        else if (c.prec == 1 && ring4) launch_conv_tile<64, 64, 2, 2, CONV_BK_SMALL, 4>(c, dim3((c.M + 63) / 64, (c.Npad + 63) / 64, c.splits), s);
-        else if (c.prec == 1 && ring3) launch_conv_tile<64, 64, 2, 2, CONV_BK_SMALL, 3>(c, dim3((c.M + 63) / 64, (c.Npad + 63) / 64, c.splits), s);
-        else
-#endif
-        launch_conv_tile<64, 64, 2, 2, CONV_BK_SMALL>(c, dim3((c.M + 63) / 64, (c.Npad + 63) / 64, c.splits), s);
+        launch_conv_tile<64, 64, 2, 2>(c, dim3((c.M + 63) / 64, (c.Npad + 63) / 64, c.splits), s);
         conv_count(c.splits == 1 ? FRLW_CONV_PATH_64X64 : vec ? FRLW_CONV_PATH_SPLIT_VEC : FRLW_CONV_PATH_SPLIT_SCALAR);
         if (c.splits > 1) {
             if (vec) hipLaunchKernelGGL(k_splitk_reduce<true>, dim3(conv_grid_1d((long long)c.M * c.Cout / 4)), dim3(256), 0, s, c);
