@@ -26,6 +26,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <atomic>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -94,6 +95,7 @@ struct FocusStemArgs {
     float *y; int Cout, y_cs, y_co;      // NHWC view of the output, Ho = H / 2, Wo = W / 2
     int tiles_x, tiles_y, n_tiles;
     int prec;                            // 1: w is the split bf16 image of the operand (conv_mfma.h), three bf16 MFMAs per product
+    int npad;                            // columns of the operand: 32, or 64 (k_focus_stem_wide)
 };
 
 // floats of LDS in front of the patch: the weight operand (P = 1: its split image, ceil16(K) rows, + the quad offset table)
@@ -206,6 +208,171 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 8))) voi
             }
         }
     }
+}
+
+// The same walk for the stems k_focus_stem does not take: up to 64 output channels (the Darknet-21 stem of the AED recipes) and
+// C0 = 4, 8 (their 2- and 4-bin inputs).  NA = accumulator tiles of 32 channels per wavefront:
+//   NA = 2: the whole (9 * 4 C0, 64) operand is resident and channels 0-31 / 32-63 are two f32x16 accumulators fed from ONE read of
+//           the patch (one float4 per four k in float32, one split of the quad pair per bf16 k-step) -- the A side of the LDS
+//           traffic and the bf16 split are paid once per 64 channels.  C0 <= 10: 90 KiB of weights + 31 KiB of patch at C0 = 10.
+//   NA = 1: the workgroup keeps ONE 32-column half of the operand, half = blockIdx.x % (npad / 32).  With npad = 64 (C0 = 16, whose
+//           144 KiB operand leaves no room for the 48 KiB patch in the CU's 160 KiB) two workgroups walk the same tiles, one per
+//           half, and the input is read twice -- the second time out of L2.  With npad = 32 it is k_focus_stem for C0 = 4, 8.
+template <int C0, int P, int NA> constexpr int focus_stem_wide_w_floats()
+{
+    return P == 1 ? (9 * 4 * C0 + 15) / 16 * 16 * 32 * NA + (9 * C0 + 7) / 4 * 4 : 9 * 4 * C0 * 32 * NA;
+}
+
+template <int C0, int P, int NA>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 8))) void k_focus_stem_wide(FocusStemArgs a)
+{
+    constexpr int CF = 4 * C0, PS = CF + 4, TH = 8, TW = 16, PH = TH + 2, PW = TW + 2, KT = 9 * CF, NL = 32 * NA;
+    constexpr int QT = CF / 4, NQ = 9 * QT, NS = (NQ + 3) / 4; // P = 1: quads per tap, quads, bf16 k-steps of 16 k = 4 quads
+    static_assert(C0 % 2 == 0, "quads are paired");
+    extern __shared__ __attribute__((aligned(16))) float fsw_lds[];
+    float *Ws = fsw_lds, *patch = fsw_lds + focus_stem_wide_w_floats<C0, P, NA>();
+    int *qoff = (int *)(fsw_lds + NS * 16 * NL); // P = 1: float offset of quad g inside the patch, relative to the tap-(0, 0) pixel
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int halves = a.npad / NL, half = blockIdx.x % halves, wg = blockIdx.x / halves, n_wg = gridDim.x / halves;
+    const int c0 = 32 * half; // first output channel (= operand column) of this workgroup
+    if (P == 1) { // rows of NL records out of rows of npad
+        for (int i = tid; i < NS * 4 * NL; i += 256) ((uint4 *)Ws)[i] = ((const uint4 *)a.w)[(i / NL) * a.npad + c0 + i % NL];
+        for (int g = tid; g < NQ; g += 256) { const int tap = g / QT; qoff[g] = ((tap / 3) * PW + tap % 3) * PS + 4 * (g - tap * QT); }
+    } else {
+        for (int i = tid; i < KT * (NL / 4); i += 256)
+            ((float4 *)Ws)[i] = ((const float4 *)a.w)[(i / (NL / 4)) * (a.npad / 4) + c0 / 4 + i % (NL / 4)];
+    }
+    const int Ho = a.H / 2, Wo = a.W / 2;
+    const int fh = lane >> 5, m = lane & 31, n = lane & 31;
+    const int pp0 = (2 * wv + (m >> 4)) * PW + (m & 15);
+    float bias[NA];
+#pragma unroll
+    for (int i = 0; i < NA; ++i) bias[i] = c0 + 32 * i + n < a.Cout ? a.bias[c0 + 32 * i + n] : 0.0f;
+    // the patch fill of k_focus_stem: this thread's items are fixed but for the tile origin; the NEXT tile's values are fetched
+    // into registers while the current tile is multiplied
+    constexpr int NI = (C0 * 2 * PH * PW + 255) / 256;
+    int it_src[NI], it_dst[NI], it_yx[NI];
+#pragma unroll
+    for (int u = 0; u < NI; ++u) {
+        const int i = tid + 256 * u;
+        const int jx = i % PW, r = i / PW, iy = r % (2 * PH), c = r / (2 * PH);
+        it_src[u] = (c * a.H + iy) * a.W + 2 * jx;
+        it_dst[u] = ((iy >> 1) * PW + jx) * PS + (iy & 1) * C0 + c;
+        it_yx[u] = i < C0 * 2 * PH * PW ? (iy << 16) | (2 * jx) : -1;
+    }
+    float2 pv[NI];
+    auto fetch = [&](int tile) {
+        const int b = tile / (a.tiles_x * a.tiles_y), tr = tile - b * (a.tiles_x * a.tiles_y);
+        const int y0 = 2 * ((tr / a.tiles_x) * TH - 1), x0 = 2 * ((tr % a.tiles_x) * TW - 1);
+        const float *base = a.x + ((long long)b * C0 * a.H + y0) * a.W + x0;
+#pragma unroll
+        for (int u = 0; u < NI; ++u) {
+            const int y = y0 + (it_yx[u] >> 16), xc = x0 + (it_yx[u] & 0xFFFF);
+            pv[u] = make_float2(0.f, 0.f);
+            if (it_yx[u] >= 0 && (unsigned)y < (unsigned)a.H && (unsigned)xc < (unsigned)a.W) pv[u] = *(const float2 *)(base + it_src[u]);
+        }
+    };
+    auto fill = [&](float *dst) {
+#pragma unroll
+        for (int u = 0; u < NI; ++u)
+            if (it_yx[u] >= 0) { dst[it_dst[u]] = pv[u].x; dst[it_dst[u] + 2 * C0] = pv[u].y; } // px = 0: q = py; px = 1: q = py + 2
+    };
+    if (wg < a.n_tiles) fetch(wg);
+    for (int tile = wg; tile < a.n_tiles; tile += n_wg) {
+        const int b = tile / (a.tiles_x * a.tiles_y), tr = tile - b * (a.tiles_x * a.tiles_y);
+        const int fy0 = (tr / a.tiles_x) * TH, fx0 = (tr % a.tiles_x) * TW;
+        __syncthreads(); // the previous tile's reads of the patch are done (first pass: the weights are in LDS)
+        fill(patch);
+        __syncthreads();
+        if (tile + n_wg < a.n_tiles) fetch(tile + n_wg);
+        f32x16 acc[NA];
+#pragma unroll
+        for (int i = 0; i < NA; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][r] = 0.0f;
+        if constexpr (P == 1) {
+            // quads and records as in k_focus_stem; the split of the patch's quad pair serves both accumulators
+            const float *pbase = patch + pp0 * PS;
+            const uint4 *wrec = (const uint4 *)Ws + 2 * fh * NL + n;
+#pragma unroll
+            for (int st = 0; st < NS; ++st) {
+                const f32x4 q0 = *(const f32x4 *)(pbase + qoff[4 * st + fh]);
+                f32x4 q1 = {0.0f, 0.0f, 0.0f, 0.0f};
+                if (4 * st + 2 < NQ) q1 = *(const f32x4 *)(pbase + qoff[4 * st + 2 + fh]); // (compile-time: the tail step of K = 360)
+                u32x4 ah, al;
+                conv_split8(q0, q1, ah, al);
+#pragma unroll
+                for (int i = 0; i < NA; ++i) {
+                    const uint4 bh4 = wrec[st * 4 * NL + 32 * i], bl4 = wrec[st * 4 * NL + NL + 32 * i];
+                    const u32x4 bh = {bh4.x, bh4.y, bh4.z, bh4.w}, bl = {bl4.x, bl4.y, bl4.z, bl4.w};
+                    acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, al), __builtin_bit_cast(bf16x8, bh), acc[i], 0, 0, 0);
+                    acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah), __builtin_bit_cast(bf16x8, bl), acc[i], 0, 0, 0);
+                    acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah), __builtin_bit_cast(bf16x8, bh), acc[i], 0, 0, 0);
+                }
+            }
+        } else
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const float *prow = patch + (pp0 + (t / 3) * PW + (t % 3)) * PS + fh * 4;
+            const float *wrow = Ws + (t * CF + 4 * fh) * NL + n;
+#pragma unroll
+            for (int j = 0; j < C0 / 2; ++j) {
+                const float4 av = *(const float4 *)(prow + 8 * j);
+                const float ae[4] = {av.x, av.y, av.z, av.w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int i = 0; i < NA; ++i)
+                        acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(ae[e], wrow[(8 * j + e) * NL + 32 * i], acc[i], 0, 0, 0);
+            }
+        }
+        // C/D layout of the 32x32 MFMA: col = lane & 31 (channel), row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5) (pixel of the wave)
+#pragma unroll
+        for (int i = 0; i < NA; ++i) {
+            const int ch = c0 + 32 * i + n;
+            if (ch < a.Cout) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int pm = (r & 3) + 8 * (r >> 2) + 4 * fh;
+                    const int oy = fy0 + 2 * wv + (pm >> 4), ox = fx0 + (pm & 15);
+                    if (oy < Ho && ox < Wo)
+                        a.y[(((long long)b * Ho + oy) * Wo + ox) * a.y_cs + a.y_co + ch] = act_apply(acc[i][r] + bias[i], ACT_SILU);
+                }
+            }
+        }
+    }
+}
+
+// which kernel a Focus + stem shape runs on: 0 = none (Focus and a convolution), 1 = k_focus_stem, 2 = k_focus_stem_wide; for 2,
+// na = accumulator tiles per wavefront and lds = its dynamic LDS in bytes
+inline int focus_stem_form(int C, int Cout, int prec, int *na, size_t *lds)
+{
+    if (Cout < 1 || Cout > 64 || (C != 4 && C != 8 && C != 10 && C != 16)) return 0;
+    if (Cout <= 32 && (C == 10 || C == 16)) return 1;
+    const int npad = Cout <= 32 ? 32 : 64;
+    // measured slower than Focus + convolution (batch 32, 256 x 320: 0.356 against 0.349 ms): the half-per-workgroup
+    // form in the bf16x3 arithmetic, whose shorter MFMA time no longer hides the second read of the input
+    if (C == 16 && npad == 64 && prec == 1) return 0;
+    *na = (npad == 64 && C != 16) ? 2 : 1; // C = 16: the 64-column operand does not fit beside the patch, one half per workgroup
+    const int nl = 32 * *na, k16 = (36 * C + 15) / 16 * 16;
+    const size_t wfl = prec == 1 ? (size_t)k16 * nl + (size_t)(9 * C + 7) / 4 * 4 : (size_t)36 * C * nl;
+    *lds = (wfl + (size_t)180 * (4 * C + 4)) * sizeof(float);
+    return *lds <= 160 * 1024 ? 2 : 0; // (the CU's LDS; hipFuncSetAttribute is asked at launch and its refusal is an error)
+}
+
+// the instantiation behind (C, prec, na) of focus_stem_form's form 2; NULL: none
+using FocusStemWideFn = void (*)(FocusStemArgs);
+template <int C0, int NA> inline FocusStemWideFn focus_stem_wide_prec(int prec)
+{
+    return prec == 1 ? (FocusStemWideFn)k_focus_stem_wide<C0, 1, NA> : (FocusStemWideFn)k_focus_stem_wide<C0, 0, NA>;
+}
+inline FocusStemWideFn focus_stem_wide_kernel(int C, int prec, int na)
+{
+    if (C == 16) return na == 1 ? focus_stem_wide_prec<16, 1>(prec) : nullptr;
+    if (C == 10) return na == 2 ? focus_stem_wide_prec<10, 2>(prec) : nullptr;
+    if (C == 8) return na == 2 ? focus_stem_wide_prec<8, 2>(prec) : focus_stem_wide_prec<8, 1>(prec);
+    if (C == 4) return na == 2 ? focus_stem_wide_prec<4, 2>(prec) : focus_stem_wide_prec<4, 1>(prec);
+    return nullptr;
 }
 
 // BFM stem, per-pixel part (core/Others/Temporal_Active_Focus.py:62-127, Temporal_Active_Focus_connect.forward
@@ -862,12 +1029,26 @@ int frlw_det_add_focus_stem(frlw_detector_t *d, int src_buf, int C, int H, int W
                             int Cout, int dst_buf, int dst_cs, int dst_co)
 {
     if (!d || !w_dev || !bias_dev || (H & 1) || (W & 1) || Cout < 1) return FRLW_ERR_ARG;
-    if ((C != 10 && C != 16) || Cout > 32) return FRLW_ERR_UNSUPPORTED; // other stems: frlw_det_add_focus + frlw_det_add_conv
+    int na = 1; size_t wide_lds = 0;
+    const int form = focus_stem_form(C, Cout, d->prec, &na, &wide_lds);
+    if (form == 0) return FRLW_ERR_UNSUPPORTED; // other stems: frlw_det_add_focus + frlw_det_add_conv
+    if (form == 2) { // the dynamic LDS is asked for HERE, where the builder can still take the unfused pair
+        const FocusStemWideFn kern = focus_stem_wide_kernel(C, d->prec, na);
+        if (!kern) return FRLW_ERR_UNSUPPORTED;
+        int n_dev = 0;
+        if (hipGetDeviceCount(&n_dev) == hipSuccess && n_dev > 0) { // (no device: a plan built for its op list, never run)
+            if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wide_lds) != hipSuccess) {
+                (void)hipGetLastError();
+                return FRLW_ERR_UNSUPPORTED;
+            }
+        } else (void)hipGetLastError();
+    }
     Op op = {};
     op.type = OP_FOCUS_STEM; op.src = src_buf; op.dst = dst_buf; op.C = C;
     FocusStemArgs &a = op.fstem;
     a.H = H; a.W = W; a.w = w_dev; a.bias = bias_dev; a.Cout = Cout; a.y_cs = dst_cs; a.y_co = dst_co;
-    a.prec = d->prec; // 1: w_dev is the split image of the (9 * 4 C, 32) operand (frlw_conv_split_operand)
+    a.prec = d->prec; // 1: w_dev is the split image of the (9 * 4 C, npad) operand (frlw_conv_split_operand)
+    a.npad = Cout <= 32 ? 32 : 64;
     a.tiles_x = (W / 2 + 15) / 16; a.tiles_y = (H / 2 + 7) / 8;
     op.lane = d->cur_lane;
     d->ops.push_back(op);
@@ -1032,6 +1213,17 @@ int frlw_det_run(const frlw_detector_t *d, int B, void *const *bufs, int n_bufs,
             a.x = buf(op.src); a.y = buf(op.dst);
             if (!a.x || !a.y) return FRLW_ERR_ARG;
             a.n_tiles = B * a.tiles_x * a.tiles_y;
+            int na = 1; size_t wide_lds = 0;
+            if (focus_stem_form(op.C, a.Cout, a.prec, &na, &wide_lds) == 2) {
+                const int halves = a.npad / (32 * na), per_cu = wide_lds <= 80 * 1024 ? 2 : 1;
+                const int wgs = a.n_tiles < 256 * per_cu / halves ? a.n_tiles : 256 * per_cu / halves;
+                const FocusStemWideFn kern = focus_stem_wide_kernel(op.C, a.prec, na);
+                if (!kern) return FRLW_ERR_UNSUPPORTED; // (frlw_det_add_focus_stem accepts only what has a kernel)
+                // (asked and checked once in frlw_det_add_focus_stem; the attribute is per device, so it is set again here)
+                (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wide_lds);
+                hipLaunchKernelGGL(kern, dim3(wgs * halves), dim3(256), wide_lds, s, a);
+                break;
+            }
             const int cf = 4 * op.C;
             const int wfl = a.prec == 1 ? (op.C == 10 ? focus_stem_w_floats<10, 1>() : focus_stem_w_floats<16, 1>()) : 9 * cf * 32;
             const size_t lds = ((size_t)wfl + (size_t)180 * (cf + 4)) * sizeof(float);

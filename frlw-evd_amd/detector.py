@@ -177,8 +177,92 @@ class DetectorEngine:
         self.ops_meta.append(("bfm", H * W, 4 * er, 0, 0))
         return f
 
+    def _spp(self, spp, src, dst=None):
+        """SPPBottleneck: conv1 writes the first quarter of the pool buffer, one kernel adds the three pools, conv2 reads it
+        (into `dst`, or a new buffer)."""
+        hid = spp.conv1.conv.out_channels
+        assert [m.kernel_size for m in spp.m] == [5, 9, 13]
+        sppcat = self._new_buf(src.h, src.w, 4 * hid)
+        self._baseconv(spp.conv1, src, sppcat.slice(0, hid))
+        _lib.check(self.lib.frlw_det_add_spp_pool(self.handle, sppcat.buf, sppcat.cs, hid, src.h, src.w), "spp")
+        self.ops_meta.append(("spp", src.h * src.w, hid, 0, 0))
+        if dst is None:
+            dst = self._new_buf(src.h, src.w, spp.conv2.conv.out_channels)
+        self._baseconv(spp.conv2, sppcat, dst)
+        return dst
+
+    def _neck_cats(self, H, W, c3, c4):
+        """The neck's four concat buffers; the backbones write dark3 / dark4 straight into the second halves of the first two."""
+        h3, w3, h4, w4, h5, w5 = H // 8, W // 8, H // 16, W // 16, H // 32, W // 32
+        cat_p3 = self._new_buf(h3, w3, 2 * c3)   # [upsample(fpn_out1) | dark3]
+        cat_p4 = self._new_buf(h4, w4, 2 * c4)   # [upsample(fpn_out0) | dark4]
+        cat_n3 = self._new_buf(h4, w4, 2 * c3)   # [bu_conv2(pan_out2) | fpn_out1]
+        cat_n4 = self._new_buf(h5, w5, 2 * c4)   # [bu_conv1(pan_out1) | fpn_out0]
+        return cat_p3, cat_p4, cat_n3, cat_n4
+
+    def _backbone_csp(self, bb, stem, H, W, c3, c4, c5):
+        """CSPDarknet behind its stem (darknet.py:270-354): (dark3, dark4, dark5) and the neck's concat buffers."""
+        c = stem.c
+        h2, w2 = H // 4, W // 4
+        d2a = self._new_buf(h2, w2, 2 * c)
+        self._baseconv(bb.dark2[0], stem, d2a)
+        d2 = self._new_buf(h2, w2, 2 * c)
+        self._csp(bb.dark2[1], d2a, d2)
+        # the three backbone outputs are written straight into the neck's concat buffers
+        h3, w3, h4, w4, h5, w5 = H // 8, W // 8, H // 16, W // 16, H // 32, W // 32
+        cats = self._neck_cats(H, W, c3, c4)
+        d3a = self._new_buf(h3, w3, c3)
+        self._baseconv(bb.dark3[0], d2, d3a)
+        d3 = cats[0].slice(c3, c3)
+        self._csp(bb.dark3[1], d3a, d3)
+        d4a = self._new_buf(h4, w4, c4)
+        self._baseconv(bb.dark4[0], d3, d4a)
+        d4 = cats[1].slice(c4, c4)
+        self._csp(bb.dark4[1], d4a, d4)
+        d5a = self._new_buf(h5, w5, c5)
+        self._baseconv(bb.dark5[0], d4, d5a)
+        d5b = self._spp(bb.dark5[1], d5a)
+        d5 = self._new_buf(h5, w5, c5)
+        self._csp(bb.dark5[2], d5b, d5)
+        return (d3, d4, d5), cats
+
+    def _chain(self, mods, src, dst):
+        """A Darknet stage (darknet.py:76-97): BaseConvs, ResLayers and the SPP block in sequence; the last layer writes `dst`.
+        A ResLayer is two convolutions, the second with the block's input as residual."""
+        from .yolox.network_blocks import BaseConv, ResLayer, SPPBottleneck
+        flat = []
+        for m in mods:
+            flat += list(m) if isinstance(m, torch.nn.Sequential) else [m]
+        for i, m in enumerate(flat):
+            last = i == len(flat) - 1
+            if isinstance(m, BaseConv):
+                s = m.conv.stride[0]
+                out = dst if last else self._new_buf(src.h // s, src.w // s, m.conv.out_channels)
+                self._baseconv(m, src, out)
+            elif isinstance(m, ResLayer):
+                mid = self._new_buf(src.h, src.w, m.layer1.conv.out_channels)
+                self._baseconv(m.layer1, src, mid)
+                out = dst if last else self._new_buf(src.h, src.w, src.c)
+                self._baseconv(m.layer2, mid, out, res=src)
+            elif isinstance(m, SPPBottleneck):
+                out = self._spp(m, src, dst if last else None)
+            else:
+                raise NotImplementedError(f"{type(m).__name__} in a Darknet stage")
+            src = out
+        return src
+
+    def _backbone_darknet(self, bb, stem, H, W, c3, c4, c5):
+        """Darknet-21 behind its stem (darknet.py:14-117): (dark3, dark4, dark5) and the neck's concat buffers."""
+        d2 = self._chain(bb.dark2, stem, self._new_buf(H // 4, W // 4, bb.dark2[0].conv.out_channels))
+        cats = self._neck_cats(H, W, c3, c4)
+        d3 = self._chain(bb.dark3, d2, cats[0].slice(c3, c3))
+        d4 = self._chain(bb.dark4, d3, cats[1].slice(c4, c4))
+        d5 = self._chain(bb.dark5, d4, self._new_buf(H // 32, W // 32, c5))
+        return (d3, d4, d5), cats
+
     def build(self, in_shape):
         """in_shape = (C, H, W) of one image (the network input without the trailing singleton dims)."""
+        from .yolox.darknet import CSPDarknet, Darknet
         net = self.net
         bb, neck, head = net.backbone, net.neck, net.head
         cin, H, W = in_shape
@@ -186,8 +270,8 @@ class DetectorEngine:
         lib = self.lib
         self._shapes = [cin * H * W]
         x_in = 0
-        # ---- backbone (darknet.py:270-354)
-        if hasattr(bb.stem, "trans_up"):  # BFM stem (yolox_taf_bfm): fused per-pixel mix, Focus layout out
+        # ---- stem (network_blocks.py:196-221; darknet.py:45,292)
+        if hasattr(bb.stem, "trans_up"):  # BFM stem (the *_taf_bfm recipes): fused per-pixel mix, Focus layout out
             f = self._bfm_front(bb.stem, x_in, cin, H, W)
         else:
             f = None
@@ -199,7 +283,7 @@ class DetectorEngine:
             if isinstance(sc.act, torch.nn.SiLU) and sc.conv.kernel_size == (3, 3) and sc.conv.stride == (1, 1):
                 w, b = fold_bn(sc.conv, sc.bn)
                 wm, npad = gemm_weight(w)
-                if npad == 32:
+                if npad <= 64:
                     rc = lib.frlw_det_add_focus_stem(self.handle, x_in, cin, H, W, self._operand(wm), self._dev(b), c, stem.buf,
                                                      stem.cs, stem.co)
                     if rc != _lib.FRLW_ERR_UNSUPPORTED:
@@ -215,39 +299,17 @@ class DetectorEngine:
                 self.ops_meta.append(("focus", H * W // 4, 4 * cin, 0, 0))
         if not fused:
             self._baseconv(bb.stem.conv, f, stem)
-        h2, w2 = H // 4, W // 4
-        d2a = self._new_buf(h2, w2, 2 * c)
-        self._baseconv(bb.dark2[0], stem, d2a)
-        d2 = self._new_buf(h2, w2, 2 * c)
-        self._csp(bb.dark2[1], d2a, d2)
-        # the three backbone outputs are written straight into the neck's concat buffers
-        c3, c4, c5 = 4 * c, 8 * c, 16 * c
+        # ---- backbone: the three outputs are slices of (or feed) the neck's concat buffers, whose widths the neck gives
+        c3, c4, c5 = (int(v) for v in neck.in_channels)
         h3, w3, h4, w4, h5, w5 = H // 8, W // 8, H // 16, W // 16, H // 32, W // 32
-        cat_p3 = self._new_buf(h3, w3, 2 * c3)   # [upsample(fpn_out1) | dark3]
-        cat_p4 = self._new_buf(h4, w4, 2 * c4)   # [upsample(fpn_out0) | dark4]
-        cat_n3 = self._new_buf(h4, w4, 2 * c3)   # [bu_conv2(pan_out2) | fpn_out1]
-        cat_n4 = self._new_buf(h5, w5, 2 * c4)   # [bu_conv1(pan_out1) | fpn_out0]
-        d3a = self._new_buf(h3, w3, c3)
-        self._baseconv(bb.dark3[0], d2, d3a)
-        d3 = cat_p3.slice(c3, c3)
-        self._csp(bb.dark3[1], d3a, d3)
-        d4a = self._new_buf(h4, w4, c4)
-        self._baseconv(bb.dark4[0], d3, d4a)
-        d4 = cat_p4.slice(c4, c4)
-        self._csp(bb.dark4[1], d4a, d4)
-        d5a = self._new_buf(h5, w5, c5)
-        self._baseconv(bb.dark5[0], d4, d5a)
-        spp = bb.dark5[1]
-        hid = spp.conv1.conv.out_channels
-        assert [m.kernel_size for m in spp.m] == [5, 9, 13]
-        sppcat = self._new_buf(h5, w5, 4 * hid)
-        self._baseconv(spp.conv1, d5a, sppcat.slice(0, hid))
-        _lib.check(lib.frlw_det_add_spp_pool(self.handle, sppcat.buf, sppcat.cs, hid, h5, w5), "spp")
-        self.ops_meta.append(("spp", h5 * w5, hid, 0, 0))
-        d5b = self._new_buf(h5, w5, c5)
-        self._baseconv(spp.conv2, sppcat, d5b)
-        d5 = self._new_buf(h5, w5, c5)
-        self._csp(bb.dark5[2], d5b, d5)
+        if isinstance(bb, Darknet):
+            (d3, d4, d5), cats = self._backbone_darknet(bb, stem, H, W, c3, c4, c5)
+        elif isinstance(bb, CSPDarknet):
+            (d3, d4, d5), cats = self._backbone_csp(bb, stem, H, W, c3, c4, c5)
+        else:
+            raise NotImplementedError(f"no plan builder for the backbone {type(bb).__name__}")
+        cat_p3, cat_p4, cat_n3, cat_n4 = cats
+        assert (d3.c, d4.c, d5.c) == (c3, c4, c5), ((d3.c, d4.c, d5.c), (c3, c4, c5))
         # ---- neck (yolo_pafpn.py:77-113)
         fpn_out0 = cat_n4.slice(c4, c4)
         self._baseconv(neck.lateral_conv0, d5, fpn_out0)

@@ -1,5 +1,5 @@
-"""Experiment objects of the entry points -- ``yolox(settings)`` / ``yoloxtafBFM(settings)`` with ``.train()`` /
-``.test()`` like the reference's (core/exp.py:44-391,580-591): same build steps (``configModel``, ``buildBackbone`` ...
+"""Experiment objects of the entry points -- ``basicExp`` / ``tafExp`` / ``tafBFMExp`` (the AED detector) and ``yolox`` /
+``yoloxtafBFM`` with ``.train()`` / ``.test()`` like the reference's (core/exp.py:44-470,580-591): same build steps (``configModel``, ``buildBackbone`` ...
 ``buildModel`` with DistributedDataParallel(broadcast_buffers=False)), same optimiser / LR schedule / GradScaler quirk,
 same checkpoint files and dict layout (``saveCheckpoint`` :198-210, ``loadCheckpoint`` :155-165), so checkpoints
 interchange with the reference's -- pinned by tests/golden/entry_points.json.
@@ -21,7 +21,7 @@ from torch.nn.parallel import DistributedDataParallel
 
 from .evaluator import evaluator, recorder
 from .trainer import LRScheduler
-from .yolox.darknet import CSPDarknet
+from .yolox.darknet import CSPDarknet, Darknet
 from .yolox.model import model
 from .yolox.network_blocks import Focus
 from .yolox.yolo_head import YOLOXHead
@@ -64,7 +64,8 @@ class SyntheticLoader:
 
 
 class basicExp:
-    """The parts of core/exp.py:44-391 the yolox recipes use; ``buildBackbone`` comes from the subclass."""
+    """core/exp.py:44-391: the ``basic`` recipe -- the AED detector (Darknet-21, neck and head 256 wide) on ``propheseeDataset``;
+    the other recipes override the backbone, the stem or the dataset."""
 
     def __init__(self, settings):
         self.settings = settings
@@ -143,10 +144,14 @@ class basicExp:
         self.in_channels = [256, 256, 256]
         self.out_features = ["dark3", "dark4", "dark5"]
         self.strides = [8, 16, 32]
+        self.backbone_size = 21
         self.depth = 0.33
+        self.stem_out_channels = 64
 
     def buildBackbone(self):
-        raise NotImplementedError("the AED backbone (Darknet-21) of the basic / taf recipes is out of scope; use yolox")
+        self.backbone = Darknet(self.backbone_size, self.settings.img_size, self.input_layer, in_channels=self.nr_input_channels,
+                                out_features=self.out_features, act="silu", out_channels=self.in_channels,
+                                stem_out_channels=self.stem_out_channels)
 
     def buildNeck(self):
         self.neck = YOLOPAFPN(self.depth, in_features=self.out_features, in_channels=self.in_channels, act="silu")
@@ -297,6 +302,27 @@ class basicExp:
         return result.evaluate(self.metric_fn)
 
 
+class tafExp(basicExp):
+    """core/exp.py:393-465: the AED detector on ``propheseeTafDataset`` (bins4 + bins8 files of ``generate_taf.py``)."""
+    _clip_train = False
+    _shard_val = False
+
+    def _dataset(self, mode, augment, clipping):
+        from .dataset import propheseeTafDataset
+        s = self.settings
+        return propheseeTafDataset(s.bbox_path, s.data_path, s.dataset_name, s.input_img_size, s.img_size, s.infer_time,
+                                   s.event_volume_bins, mode, augment, clipping)
+
+
+class tafBFMExp(tafExp):
+    """core/exp.py:467-470: the BFM stem in front of the AED detector."""
+
+    def __init__(self, settings):
+        super().__init__(settings)
+        from .yolox.bfm import Temporal_Active_Focus_connect
+        self.input_layer = Temporal_Active_Focus_connect
+
+
 class yolox(basicExp):
     """core/exp.py:580-586."""
 
@@ -327,5 +353,5 @@ class yoloxtafBFM(yolox):
                                    s.event_volume_bins, mode, augment, clipping)
 
 
-EXPERIMENTS = {"yolox": yolox, "yolox_taf_bfm": yoloxtafBFM}
-OTHER_RECIPES = ("basic", "taf", "taf_bfm", "yolov3", "yolov3_taf_bfm")  # AED / YOLOv3 detectors: out of scope
+EXPERIMENTS = {"basic": basicExp, "taf": tafExp, "taf_bfm": tafBFMExp, "yolox": yolox, "yolox_taf_bfm": yoloxtafBFM}
+OTHER_RECIPES = ("yolov3", "yolov3_taf_bfm")  # the YOLOv3 detector (Darknet-53): out of scope

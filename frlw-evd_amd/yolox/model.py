@@ -5,7 +5,7 @@ import time
 import torch
 import torch.nn as nn
 
-from .darknet import CSPDarknet
+from .darknet import CSPDarknet, Darknet
 from .network_blocks import Focus
 from .yolo_head import YOLOXHead
 from .yolo_pafpn import YOLOPAFPN
@@ -124,6 +124,22 @@ def build_yolox(in_channels=10, num_classes=2, radius=5.0, stem="focus"):
         backbone = CSPDarknet(in_channels, 0.33, 0.5, stem=Temporal_Active_Focus_connect)
     else:
         backbone = CSPDarknet(in_channels, 0.33, 0.5, stem=Focus)
+    neck = YOLOPAFPN(0.33, in_features=["dark3", "dark4", "dark5"], in_channels=chans, act="silu")
+    head = YOLOXHead(num_classes, in_channels=chans, act="silu", strides=[8, 16, 32], radius=radius)
+    return model(backbone, neck, None, head)
+
+
+def build_aed(in_channels=10, num_classes=2, radius=5.0, stem="focus", img_size=(256, 320)):
+    """The AED detector of the ``basic`` / ``taf`` recipes: Darknet(21, stem_out_channels=64, out_channels=[256, 256, 256]) +
+    YOLOPAFPN(0.33, [256, 256, 256]) + YOLOXHead(nc, strides [8, 16, 32], in_channels [256, 256, 256])
+    (core/exp.py:352-384).  ``stem="bfm"``: the ``taf_bfm`` recipe (core/exp.py:467-470)."""
+    chans = [256, 256, 256]
+    if stem == "bfm":
+        from .bfm import Temporal_Active_Focus_connect as stem_cls
+    else:
+        stem_cls = Focus
+    backbone = Darknet(21, img_size, stem_cls, in_channels=in_channels, out_features=["dark3", "dark4", "dark5"], act="silu",
+                       out_channels=chans, stem_out_channels=64)
     neck = YOLOPAFPN(0.33, in_features=["dark3", "dark4", "dark5"], in_channels=chans, act="silu")
     head = YOLOXHead(num_classes, in_channels=chans, act="silu", strides=[8, 16, 32], radius=radius)
     return model(backbone, neck, None, head)

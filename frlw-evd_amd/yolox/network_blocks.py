@@ -1,7 +1,7 @@
 """Building blocks of the YOLOX detector (reference: core/yolox/models/network_blocks.py).
 
 Same attribute names as the reference so checkpoints interchange: ``BaseConv.{conv,bn,act}``,
-``Bottleneck.{conv1,conv2}``, ``CSPLayer.{conv1,conv2,conv3,m}``, ``SPPBottleneck.{conv1,m,conv2}``,
+``Bottleneck.{conv1,conv2}``, ``ResLayer.{layer1,layer2}``, ``CSPLayer.{conv1,conv2,conv3,m}``, ``SPPBottleneck.{conv1,m,conv2}``,
 ``Focus.conv``.
 """
 import torch
@@ -70,6 +70,24 @@ class Bottleneck(nn.Module):
             raise RuntimeError("Bottleneck: a destination slice needs the native training path")
         y = self.conv2(self.conv1(x), into=into) if into is not None else self.conv2(self.conv1(x))
         return y + x if self.use_add else y
+
+
+class ResLayer(nn.Module):
+    """``x + layer2(layer1(x))``: 1x1 C -> C/2, 3x3 C/2 -> C (network_blocks.py:113-128) -- the Darknet-21 block of the AED
+    recipes; a ``Bottleneck`` with shortcut under the reference's other attribute names."""
+
+    def __init__(self, in_channels, act="silu"):
+        super().__init__()
+        mid_channels = in_channels // 2
+        self.layer1 = BaseConv(in_channels, mid_channels, ksize=1, stride=1, act=act)
+        self.layer2 = BaseConv(mid_channels, in_channels, ksize=3, stride=1, act=act)
+
+    def forward(self, x):
+        if self.training and x.is_cuda:
+            from . import train_ops
+            if train_ops.bottleneck_eligible(x, self.layer1, self.layer2):  # shortcut and its gradient inside the blocks' launches
+                return train_ops.bottleneck_train(x, self.layer1, self.layer2)
+        return x + self.layer2(self.layer1(x))
 
 
 class SPPBottleneck(nn.Module):

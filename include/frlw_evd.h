@@ -343,8 +343,11 @@ int frlw_det_add_focus(frlw_detector_t *d, int src_buf, int C, int H, int W, int
 int frlw_focus_nhwc(const float *x, int B, int C, int H, int W, float *y, frlw_stream_t stream);
 
 /* Focus + the stem's 3x3 BaseConv (darknet.py:292) fused: the space-to-depth image stays in LDS.  w_dev / bias_dev as for
- * frlw_det_add_conv with Cin = 4 C, k = 3, Npad = 32.  C in {10, 16} (TAF K = 5 / 8), Cout <= 32, else
- * FRLW_ERR_UNSUPPORTED (use frlw_det_add_focus + frlw_det_add_conv). */
+ * frlw_det_add_conv with Cin = 4 C, k = 3, Npad = Cout rounded up to 32.  C in {4, 8, 10, 16} (2, 4, 5, 8 bins of two
+ * polarities), Cout <= 64 (the CSPDarknet stem is 32 wide, the Darknet-21 stem 64: two 32-channel accumulators per wavefront,
+ * at C = 16 one 32-channel half per workgroup, float32 arithmetic only: in bf16x3 that form measured slower than the unfused
+ * pair), else FRLW_ERR_UNSUPPORTED (use frlw_det_add_focus + frlw_det_add_conv).  The kernel's dynamic LDS is asked for here,
+ * so a refusal of the runtime is FRLW_ERR_UNSUPPORTED of this call and not an error of frlw_det_run. */
 int frlw_det_add_focus_stem(frlw_detector_t *d, int src_buf, int C, int H, int W, const float *w_dev, const float *bias_dev,
                             int Cout, int dst_buf, int dst_cs, int dst_co);
 int frlw_det_bfm_weight_count(int C);

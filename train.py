@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Training entry point with the reference's command line (train.py:9-71): same flags, same
-``init_process_group('nccl', 'env://')`` (RCCL on ROCm), same ``Setting_train_val`` -> ``yolox(settings).train()`` /
-``yoloxtafBFM(settings).train()`` dispatch, one process per GPU, ``--nodes`` = number of GPUs dividing the global batch.
+``init_process_group('nccl', 'env://')`` (RCCL on ROCm), same ``Setting_train_val`` -> ``basicExp`` / ``tafExp`` / ``tafBFMExp`` /
+``yolox`` / ``yoloxtafBFM`` ``(settings).train()`` dispatch, one process per GPU, ``--nodes`` = number of GPUs dividing the global batch.
 
     python -m torch.distributed.run --nproc-per-node G train.py --dataset gen1 --batch_size 64 --exp_name E \\
         --exp_type yolox --event_volume_bins 8 --nodes G
@@ -61,8 +61,8 @@ def pick_experiment(exp_type):
     if exp_type in exp.EXPERIMENTS:
         return exp.EXPERIMENTS[exp_type]
     if exp_type in exp.OTHER_RECIPES:
-        raise SystemExit(f"--exp_type {exp_type}: the AED / YOLOv3 detectors are outside this build's scope "
-                         f"(SURVEY.md section 2 #15, #16); available: {', '.join(exp.EXPERIMENTS)}")
+        raise SystemExit(f"--exp_type {exp_type}: the YOLOv3 detector (Darknet-53) is outside this build's scope "
+                         f"(SURVEY.md section 2 #16); available: {', '.join(exp.EXPERIMENTS)}")
     raise SystemExit(f"unknown --exp_type {exp_type}")
 
 
