@@ -76,6 +76,13 @@ class FrlwBaseconvFuse(C.Structure):
             setattr(self, k, v if (v is None or dict(self._fields_)[k] is C.c_void_p) else int(v))
 
 
+class FrlwWeightLayoutItem(C.Structure):
+    """frlw_weight_layout_item_t: one entry of the device table frlw_conv_weight_layouts_batch reads."""
+    _fields_ = [("w", C.c_void_p), ("w_fwd", C.c_void_p), ("w_dgrad", C.c_void_p), ("Cout", C.c_int32), ("Cin", C.c_int32),
+                ("k", C.c_int32), ("dgrad_parity", C.c_int32), ("precision", C.c_int32), ("reserved", C.c_int32),
+                ("first", C.c_int64), ("w2", C.c_void_p), ("split", C.c_int32), ("reserved2", C.c_int32)]
+
+
 class FrlwEvents(C.Structure):
     _fields_ = [("data", C.c_void_p), ("n", C.c_int64), ("layout", C.c_int32),
                 ("row_stride", C.c_int32), ("xmap", C.c_void_p), ("ymap", C.c_void_p),

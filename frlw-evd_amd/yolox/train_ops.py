@@ -11,15 +11,14 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import NamedTuple, Optional
 
 import torch
 
 from .. import _lib, _pins
+from .operand_cache import layout_all_weights, native_enabled, operands_of  # noqa: F401 (layout_all_weights: the trainer calls it here)
 
 _SCRATCH = {}
-_WCACHE = {}  # id(weight parameter) -> (weakref, operand cache): forward + data-gradient layouts, rebuilt every forward
-_WCACHE_GEOM = {}  # id(weight parameter) -> what the data-gradient layout in the cache was laid out for: (version, parity)
-
 
 PRECISIONS = {"f32": 0, "bf16x3": 1}
 
@@ -39,122 +38,6 @@ def layer_precision(Cout, k, stride):
     which must be whole k-tiles of 16 (every width of the shipped networks is); other widths keep the float32 MFMA."""
     p = conv_precision()
     return p if (p == 0 or not (k == 3 and stride == 2) or Cout % 16 == 0) else 0
-
-
-def _weight_cache(lib, weight, Cin, Cout, k):
-    import weakref
-    key = id(weight)
-    hit = _WCACHE.get(key)
-    n = lib.frlw_baseconv_weight_cache_floats(Cin, Cout, k, 1)  # room for either precision
-    if hit is None or hit[0]() is not weight or hit[1].numel() < n or hit[1].device != weight.device:
-        buf = torch.empty(int(n), dtype=torch.float32, device=weight.device)
-        if hit is not None:
-            _pins.retire(hit[1])  # a live HIP graph may still launch kernels on the old cache
-        _WCACHE[key] = (weakref.ref(weight, lambda _r, key=key: _WCACHE.pop(key, None)), buf)
-        return buf
-    return hit[1]
-
-
-_PAIRS = {}  # id(first weight of a stacked pair) -> (weakref of it, weakref of the second weight); set by the pair's forward
-
-
-def _pair_second(w):
-    """The second weight of the stacked pair whose first weight is ``w`` (None: ``w`` is an ordinary weight)."""
-    refs = _PAIRS.get(id(w))
-    if refs is None:
-        return None
-    w2 = refs[1]()
-    if refs[0]() is not w or w2 is None:  # (an id reused by another tensor, or a pair whose second weight is gone)
-        _PAIRS.pop(id(w), None)
-        return None
-    return w2
-
-
-def _ver(w, w2=None):
-    return w._version if w2 is None else (w._version, w2._version)
-
-
-_WREADY = {}  # id(weight parameter) -> (version, parity, cache data_ptr) the batched layout below has laid the cache out for
-_PLANS = {}  # id(model) -> (weakref, item table on the device, total elements, [(weight, parity, cache, weight pointer)])
-
-
-def _layout_plan(model):
-    """One table entry per natively trained BaseConv weight of `model` whose operand cache exists (= that has run one
-    forward): frlw_weight_layout_item_t {w, w_fwd, w_dgrad, Cout, Cin, k, parity, precision, reserved, first, w2, split, reserved2};
-    the first weight of a stacked pair stands for both (Cout = the pair's channels, w2 / split = the second weight)."""
-    import struct
-    import weakref
-    lib = _lib.load()
-    rows, blob, first = [], b"", 0
-    for mod in model.modules():
-        conv, bn = getattr(mod, "conv", None), getattr(mod, "bn", None)
-        if not isinstance(conv, torch.nn.Conv2d) or not isinstance(bn, torch.nn.BatchNorm2d):
-            continue
-        w = conv.weight
-        hit, geom = _WCACHE.get(id(w)), _WCACHE_GEOM.get(id(w))
-        if hit is None or geom is None or hit[0]() is not w or not w.is_cuda or not w.is_contiguous() or w.dtype != torch.float32:
-            continue
-        Cout, Cin, k, _ = w.shape
-        w2 = _pair_second(w)
-        split = 0
-        if w2 is not None:
-            if not (w2.is_cuda and w2.is_contiguous() and w2.dtype == torch.float32 and isinstance(geom[0], tuple)):
-                continue
-            split, Cout = Cout, Cout + w2.shape[0]
-        elif isinstance(geom[0], tuple):
-            continue  # the cache was last laid out for a pair that is gone
-        cache = hit[1]
-        prec = geom[2]
-        n_f, n_d = lib.frlw_conv_operand_floats(k * k * Cin, Cout, prec), lib.frlw_conv_operand_floats(k * k * Cout, Cin, prec)
-        if cache.numel() < n_f + n_d:
-            continue
-        blob += struct.pack("<QQQiiiiiiqQii", w.data_ptr(), cache.data_ptr(), cache.data_ptr() + 4 * n_f, Cout, Cin, k, geom[1], prec, 0, first,
-                            w2.data_ptr() if w2 is not None else 0, split, 0)
-        first += n_f + n_d
-        rows.append((w, (geom[1], prec), cache, w.data_ptr(), w2, w2.data_ptr() if w2 is not None else 0))
-    if not rows:
-        return None
-    import numpy as np
-    table = torch.from_numpy(np.frombuffer(blob, dtype=np.uint8).copy()).to(rows[0][0].device)
-    return (weakref.ref(model), table, first, rows)
-
-
-def layout_all_weights(model):
-    """Lay out the GEMM operands of EVERY BaseConv weight of `model` in one launch (call it once per step, before the
-    forward: the per-layer forwards then find their cache ready and skip their own layout kernel -- 74 launches of ~5 us).
-    Does nothing until the layers have run once (their caches are created by the first forward), or off the GPU."""
-    if not native_enabled():
-        return False
-    plan = _PLANS.get(id(model))
-    stale = plan is None or plan[0]() is not model
-    if not stale:
-        for w, parity, cache, ptr, w2, ptr2 in plan[3]:  # parity = (parity class, precision) the entry was written for
-            hit, geom = _WCACHE.get(id(w)), _WCACHE_GEOM.get(id(w))
-            if (hit is None or hit[1] is not cache or geom is None or geom[1:] != parity or w.data_ptr() != ptr
-                    or _pair_second(w) is not w2 or (w2 is not None and w2.data_ptr() != ptr2) or isinstance(geom[0], tuple) != (w2 is not None)):
-                stale = True
-                break
-    if stale:
-        if plan is not None:
-            _pins.retire(plan[1])  # the item table a captured layout launch reads
-        plan = _layout_plan(model)
-        if plan is None:
-            _PLANS.pop(id(model), None)
-            return False
-        _PLANS[id(model)] = plan
-    _, table, total, rows = plan
-    lib = _lib.load()
-    _lib.check(lib.frlw_conv_weight_layouts_batch(table.data_ptr(), len(rows), total, _stream(table.device)), "weight_layouts_batch")
-    for w, parity, cache, _ptr, w2, _ptr2 in rows:
-        _WREADY[id(w)] = (_ver(w, w2), parity, cache.data_ptr())
-        _WCACHE_GEOM[id(w)] = (_ver(w, w2), *parity)
-    return True
-
-
-def _bump_versions(*tensors):
-    """Advance the in-place version counters of buffers a kernel has written through raw pointers (no launch)."""
-    for t in tensors:
-        torch.autograd.graph.increment_version(t)
 
 
 def _scratch(dev, key, numel, dtype):
@@ -201,17 +84,12 @@ def _rows_in_place(t):
     return t, 0
 
 
-def pad32(n):
-    return (n + 31) // 32 * 32
-
-
-def native_enabled():
-    return os.environ.get("FRLW_NATIVE_TRAIN", "1") != "0"
-
-
-class _Rec:
+class _Rec(NamedTuple):
     """What one BaseConv forward leaves for its backward beside the saved tensors (x, z, w, gamma, beta, stats)."""
-    __slots__ = ("geom", "wcache", "wparity", "wversion", "weight_ref", "weight2_ref", "split")
+    geom: tuple      # (B, Cin, H, W, Cout, k, stride)
+    operands: object  # the weight's operand_cache.WeightOperands
+    key: tuple       # ... and the operand_cache.Key this forward left in its cache
+    split: int       # channels of the first block of a stacked pair, else 0
 
 
 def _slice_ok(out, shape):
@@ -221,7 +99,7 @@ def _slice_ok(out, shape):
 def _fwd_one(x, weight, gamma, beta, stride, eps, run_mean, run_var, momentum, tracked, residual=None, out=None, pair=None):
     """One frlw_baseconv_train_fwd call: (y, tensors to save, _Rec).  ``x``: float32 NHWC storage.  ``residual``: added to y in
     the pass that writes it; ``out``: a (B, Cout, Ho, Wo) channel slice of a wider channels_last tensor y is written into.
-    ``pair`` = (weight2, gamma2, beta2, (eps2, run_mean2, run_var2, momentum2, tracked2), out2): a SECOND BaseConv reading the same
+    ``pair`` = (weight2, gamma2, beta2, BnCfg of the second block, out2): a SECOND BaseConv reading the same
     x, stacked along the output channels (frlw_baseconv_fuse_t::split) -- returns ((y, y2), tensors to save, _Rec)."""
     lib = _lib.load()
     dev = x.device
@@ -234,8 +112,7 @@ def _fwd_one(x, weight, gamma, beta, stride, eps, run_mean, run_var, momentum, t
     g = gamma.detach().float().contiguous()
     b = beta.detach().float().contiguous()
     z = torch.empty((B, Cout, Ho, Wo), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
-    fuse = None
-    extra = ()
+    fuse, extra = None, ()
     y_shape = (B, C1, Ho, Wo)
     if residual is not None or out is not None:
         res, res_rs = (None, 0) if residual is None else _rows_in_place(residual)
@@ -253,46 +130,27 @@ def _fwd_one(x, weight, gamma, beta, stride, eps, run_mean, run_var, momentum, t
         y2 = out2 if out2 is not None else torch.empty(y2_shape, dtype=torch.float32, device=dev, memory_format=torch.channels_last)
         fuse = fuse if fuse is not None else _lib.FrlwBaseconvFuse()
         fuse.split, fuse.w2, fuse.gamma2, fuse.beta2 = C1, w2.data_ptr(), g2.data_ptr(), b2.data_ptr()
-        fuse.running_mean2 = cfg2[1].data_ptr() if cfg2[1] is not None else None
-        fuse.running_var2 = cfg2[2].data_ptr() if cfg2[2] is not None else None
-        fuse.num_batches_tracked2 = cfg2[4].data_ptr() if cfg2[4] is not None else None
+        fuse.running_mean2 = cfg2.running_mean.data_ptr() if cfg2.running_mean is not None else None
+        fuse.running_var2 = cfg2.running_var.data_ptr() if cfg2.running_var is not None else None
+        fuse.num_batches_tracked2 = cfg2.tracked.data_ptr() if cfg2.tracked is not None else None
         fuse.y2, fuse.y2_row_stride = y2.data_ptr(), (y2.stride()[3] if out2 is not None else 0)
-        assert cfg2[0] == eps and cfg2[3] == momentum and (cfg2[1] is None) == (run_mean is None)
+        assert cfg2.eps == eps and cfg2.momentum == momentum and (cfg2.running_mean is None) == (run_mean is None)
         extra = (w2, g2, b2)
-        import weakref
-        _PAIRS[id(weight)] = (weakref.ref(weight), weakref.ref(weight2))
     stats = torch.empty((3, Cout), dtype=torch.float32, device=dev)  # mean, biased variance, invstd
     sc = _scratch(dev, "block", lib.frlw_baseconv_train_scratch_bytes(B, H, W, Cin, Cout, k, stride), torch.uint8)
-    wc = _weight_cache(lib, weight, Cin, Cout, k)  # both GEMM operands of this weight, laid out once per step
-    parity = int(lib.frlw_conv2d_dgrad_parity(k, stride, H, W))
-    prec = layer_precision(Cout, k, stride)
-    # laid out already by layout_all_weights() for exactly this weight version, parity class, precision and buffer?
-    weight2 = pair[0] if pair is not None else None
-    if pair is None:
-        _PAIRS.pop(id(weight), None)  # this weight runs on its own (again): its cache is laid out for itself
-    ver = _ver(weight, weight2)
-    ready = (_WREADY.get(id(weight)) == (ver, (parity, prec), wc.data_ptr()) and w.data_ptr() == weight.data_ptr()
-             and (weight2 is None or extra[0].data_ptr() == weight2.data_ptr()))
+    ops = operands_of(lib, weight, pair[0] if pair is not None else None, Cin, Cout, k)  # both GEMM operands, laid out once per step
+    # (the data-gradient operand depends on the parity class of (k, stride, H, W): a shared layer on an input of another parity re-lays it)
+    key = ops.key(int(lib.frlw_conv2d_dgrad_parity(k, stride, H, W)), layer_precision(Cout, k, stride))
+    # laid out already by layout_all_weights() (a captured step replays that launch, never a forward's own) for exactly this?
+    ready = ops.batched and ops.holds(key) and key.ptrs == tuple(t.data_ptr() for t in (w, *extra[:1]))
     _lib.check(lib.frlw_baseconv_train_fwd(x.data_ptr(), None if ready else w.data_ptr(), g.data_ptr(), b.data_ptr(), C.c_float(eps), B, H, W,
-                                           Cin, Cout, k, stride, z.data_ptr(), y.data_ptr(), stats[0].data_ptr(),
-                                           stats[1].data_ptr(), stats[2].data_ptr(),
-                                           run_mean.data_ptr() if run_mean is not None else None,
+                                           Cin, Cout, k, stride, z.data_ptr(), y.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(),
+                                           stats[2].data_ptr(), run_mean.data_ptr() if run_mean is not None else None,
                                            run_var.data_ptr() if run_var is not None else None, C.c_float(momentum),
-                                           tracked.data_ptr() if tracked is not None else None,
-                                           wc.data_ptr(), sc.data_ptr(), sc.numel(), _sk_counters(dev).data_ptr(),
-                                           C.byref(fuse) if fuse is not None else None, prec, _stream(dev)), "baseconv_train_fwd")
-    rec = _Rec()
-    rec.wcache = wc
-    # the data-gradient half of the cache depends on the parity class of (k, stride, H, W): a second forward of the same
-    # layer on an input of another parity (shared layer, multi-scale graph) re-lays it -- remember what THIS forward wrote
-    rec.wparity = (parity, prec)
-    _WCACHE_GEOM[id(weight)] = (ver, parity, prec)
-    rec.wversion = ver
-    rec.weight_ref = weight
-    rec.weight2_ref = weight2
-    rec.split = C1 if pair is not None else 0
-    rec.geom = (B, Cin, H, W, Cout, k, stride)
-    return (y if pair is None else (y, y2)), (x, z, w, g, b, stats) + extra, rec
+                                           tracked.data_ptr() if tracked is not None else None, key.cache, sc.data_ptr(), sc.numel(), _sk_counters(dev).data_ptr(),
+                                           C.byref(fuse) if fuse is not None else None, key.precision, _stream(dev)), "baseconv_train_fwd")
+    ops.written, ops.batched = key, ready
+    return (y if pair is None else (y, y2)), (x, z, w, g, b, stats) + extra, _Rec((B, Cin, H, W, Cout, k, stride), ops, key, C1 if pair is not None else 0)
 
 
 def _bwd_one(rec, saved, dy, need_dx, dx_add=None, dy2=None):
@@ -319,18 +177,14 @@ def _bwd_one(rec, saved, dy, need_dx, dx_add=None, dy2=None):
         fuse.split, fuse.w2, fuse.gamma2, fuse.beta2 = rec.split, w2.data_ptr(), g2.data_ptr(), b2.data_ptr()
         fuse.dy2, fuse.dy2_row_stride = dy2.data_ptr(), dy2_rs
     sc = _scratch(dev, "block", lib.frlw_baseconv_train_scratch_bytes(B, H, W, Cin, Cout, k, stride), torch.uint8)
-    # the operand cache belongs to the forward of THIS graph only while the weight (and the cache) are untouched
-    # since: a second forward of the same layer before this backward would have overwritten it with the same
-    # weights' layout (fine), an in-place weight update in between would not (then lay out again)
-    fresh = (_ver(rec.weight_ref, rec.weight2_ref) == rec.wversion and _WCACHE.get(id(rec.weight_ref), (None, None))[1] is rec.wcache
-             and _WCACHE_GEOM.get(id(rec.weight_ref)) == (rec.wversion, *rec.wparity))
+    # the cache still holds what the forward of THIS graph left: a second forward of the same layer since has written the same
+    # weights' layout again (fine), an in-place weight update, another parity class or a new buffer have not (lay out again)
+    fresh = rec.operands.holds(rec.key)
     _lib.check(lib.frlw_baseconv_train_bwd(dy.data_ptr(), dy_rs, x.data_ptr(), z.data_ptr(), w.data_ptr(), g.data_ptr(),
                                            b.data_ptr(), stats[0].data_ptr(), stats[2].data_ptr(), B, H, W, Cin, Cout, k,
-                                           stride, dz.data_ptr(), dx.data_ptr() if dx is not None else None,
-                                           dw.data_ptr(), dgb[0].data_ptr(), dgb[1].data_ptr(),
-                                           rec.wcache.data_ptr() if fresh else None, sc.data_ptr(),
-                                           sc.numel(), _sk_counters(dev).data_ptr(), C.byref(fuse) if fuse is not None else None,
-                                           rec.wparity[1], _stream(dev)), "baseconv_train_bwd")
+                                           stride, dz.data_ptr(), dx.data_ptr() if dx is not None else None, dw.data_ptr(), dgb[0].data_ptr(),
+                                           dgb[1].data_ptr(), rec.key.cache if fresh else None, sc.data_ptr(), sc.numel(), _sk_counters(dev).data_ptr(),
+                                           C.byref(fuse) if fuse is not None else None, rec.key.precision, _stream(dev)), "baseconv_train_bwd")
     return dx, dw, dgb[0], dgb[1]
 
 
@@ -473,9 +327,18 @@ class _PairStackTrain(torch.autograd.Function):
         return dx, dw[:h], dg[:h], db[:h], dw[h:], dg[h:], db[h:], None, None, None, None
 
 
+class BnCfg(NamedTuple):
+    """BatchNorm settings of one forward (the running buffers and the device counter: None when not tracked / not on the device)."""
+    eps: float
+    running_mean: Optional[torch.Tensor]
+    running_var: Optional[torch.Tensor]
+    momentum: float
+    tracked: Optional[torch.Tensor]
+
+
 def _bn_cfg(bn):
-    """(eps, running_mean, running_var, momentum, num_batches_tracked on the device or None) of one forward, like
-    nn.BatchNorm2d.forward; a cumulative-average module (momentum None) bumps its counter on the host here."""
+    """(BnCfg of one forward, like nn.BatchNorm2d.forward; whether it tracks running statistics); a cumulative-average module
+    (momentum None) bumps its counter on the host here."""
     track = bn.track_running_stats and bn.running_mean is not None
     momentum = 0.0
     tracked = None
@@ -488,14 +351,14 @@ def _bn_cfg(bn):
             tracked = bn.num_batches_tracked if bn.num_batches_tracked.is_cuda else None
             if tracked is None:
                 bn.num_batches_tracked += 1
-    return (bn.eps, bn.running_mean if track else None, bn.running_var if track else None, float(momentum), tracked), track
+    return BnCfg(bn.eps, bn.running_mean if track else None, bn.running_var if track else None, float(momentum), tracked), track
 
 
 def _bn_done(bn, track):
     if track:
         # the kernels wrote the running statistics through raw pointers: tell autograd's version counters, which is what the
         # eval engine's weight signature (yolox/model.py) watches -- also when only a submodule is in training mode
-        _bump_versions(bn.running_mean, bn.running_var)
+        torch.autograd.graph.increment_version((bn.running_mean, bn.running_var))  # (no launch)
 
 
 def base_conv_train(x, conv, bn, into=None):
@@ -545,8 +408,8 @@ def pair_stackable(ca, cb, cfga, cfgb):
     """Both blocks as ONE stacked block: same kernel size and input, channel counts multiples of 4, the same BatchNorm settings
     (eps, momentum, both or neither tracking running statistics, counters both on the device or both absent)."""
     return (stack_enabled() and ca.conv.kernel_size == cb.conv.kernel_size and ca.conv.out_channels % 4 == 0
-            and cb.conv.out_channels % 4 == 0 and cfga[0] == cfgb[0] and cfga[3] == cfgb[3]
-            and (cfga[1] is None) == (cfgb[1] is None) and (cfga[4] is None) == (cfgb[4] is None)
+            and cb.conv.out_channels % 4 == 0 and cfga.eps == cfgb.eps and cfga.momentum == cfgb.momentum
+            and (cfga.running_mean is None) == (cfgb.running_mean is None) and (cfga.tracked is None) == (cfgb.tracked is None)
             and layer_precision(ca.conv.out_channels + cb.conv.out_channels, ca.conv.kernel_size[0], 1) == layer_precision(ca.conv.out_channels, ca.conv.kernel_size[0], 1))
 
 

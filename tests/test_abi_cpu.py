@@ -132,6 +132,22 @@ def test_baseconv_fuse_struct_is_checked_on_the_host():
     assert fwd(good) == _lib.FRLW_ERR_WORKSPACE and bwd(good) == _lib.FRLW_ERR_WORKSPACE
 
 
+def test_weight_layout_item_matches_the_header():
+    """frlw_weight_layout_item_t as ctypes declares it: size and offsets as they follow from include/frlw_evd.h, and the bytes of
+    one made-up entry equal the little-endian packing of the header's fields in order."""
+    import ctypes as C
+    import struct
+    item = _lib.FrlwWeightLayoutItem
+    assert C.sizeof(item) == 72
+    offsets = {"w": 0, "w_fwd": 8, "w_dgrad": 16, "Cout": 24, "precision": 40, "first": 48, "w2": 56, "split": 64}
+    assert {n: getattr(item, n).offset for n in offsets} == offsets
+    row = item(w=0x7F0000001000, w_fwd=0x7F0000002000, w_dgrad=0x7F0000002A00, Cout=48, Cin=24, k=3, dgrad_parity=1, precision=1,
+               first=123456789012, w2=0x7F0000003000, split=32)
+    assert bytes(row) == struct.pack("<QQQiiiiiiqQii", 0x7F0000001000, 0x7F0000002000, 0x7F0000002A00, 48, 24, 3, 1, 1, 0,
+                                     123456789012, 0x7F0000003000, 32, 0)
+    assert bytes((item * 2)(row, item(w2=None)))[:72] == bytes(row) and bytes(item(w2=None)) == bytes(72)
+
+
 def test_conv_path_counters_match_the_header_and_start_at_zero():
     """frlw_conv_path_counts: the enum of include/frlw_evd.h and _lib.CONV_PATHS name the same counters in the same order;
     NULL / n < 1 are refused; a fresh process (nothing launched) reads all zeros, and a short buffer gets a prefix."""
