@@ -19,6 +19,7 @@ FRLW_ERR_POLARITY = -5
 FRLW_ERR_UNSUPPORTED = -6
 FRLW_ERR_SPAN = -7
 MAX_SEQUENCES = 64
+MAX_LAMDAS = 8
 
 # the FRLW_CONV_PATH_* counters of frlw_conv_path_counts, in the header's enum order (lower case, prefix dropped)
 CONV_PATHS = ("128x32", "128x128_4x1", "128x128_2x2", "64x128", "64x64", "split_vec", "split_scalar", "split_inkernel",
@@ -115,6 +116,12 @@ SYMBOLS = {
                                    _P, _SZ, _P]),
     "frlw_ev_batch_workspace_bytes": (_SZ, [_I64, _I, _I, _I, _I64]),
     "frlw_ev_encode_batch": (_I, [_EV, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _I, _I, _I, _I, _I64, _P, _P, _P, _SZ, _P]),
+    "frlw_eci_batch_workspace_bytes": (_SZ, [_I64, _I, _I, _I]),
+    "frlw_eci_encode_batch": (_I, [_EV, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _I, _I, _I, _P, _P, _P, _SZ, _P]),
+    "frlw_sae_batch_workspace_bytes": (_SZ, [_I64, _I, _I, _I]),
+    "frlw_sae_encode_batch": (_I, [_EV, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _I, _I, _I, C.POINTER(C.c_double), _I, _P, _P,
+                                  _I64, _P, _P, _P, _SZ, _P]),
+    "frlw_encoder_batch_counts": (_I, [C.POINTER(C.c_uint64)]),
     "frlw_leaky_transform": (_I, [_P, _I64, _P, _P, _P]),
     "frlw_resize_nearest_f32": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "frlw_resize_nearest_u8": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),

@@ -569,3 +569,97 @@ def encode_sae_dat(dat, shape, lamdas, memory, now, window_us, want_f32=True, wa
     if check:
         _finish(ws, "encode_sae_dat")
     return out, u8, mem_out
+
+
+# ------------------------------------------------------------------------------------------------
+# batched Event Count Image / Surface of Active Events (csrc/encoders_batch.hip)
+# ------------------------------------------------------------------------------------------------
+def _slot_workspace(need, device, slot):
+    """The workspace of ``slot`` on the current stream, grown to ``need`` bytes."""
+    key = (slot, device.index, torch.cuda.current_stream().cuda_stream)
+    ws = _WORKSPACES.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _new_workspace(ws, need, device)
+        _WORKSPACES[key] = ws
+    return ws
+
+
+def encode_eci_batch(dat, ranges, shape, want_f32=True, want_u8=False, xmap=None, ymap=None, check=True):
+    """generate_eventcountimage.py:155-180 for a batch of record windows in one launch sequence (``frlw_eci_encode_batch``):
+    window ``b`` is the records ``dat[lo:hi]`` of ``ranges[b] = (lo, hi)``; windows may overlap, nest or be empty.  Returns
+    ``(f32 (B, 2, H, W) or None, u8 or None)`` -- bit for bit what ``encode_eci_dat`` gives per window.  ``ValueError`` outside
+    1..64 windows or for a range that runs backwards or leaves ``dat``; with ``check`` an event outside the frame raises
+    ``IndexError``, unchecked callers owe a ``raise_deferred()``.  ``NotImplementedError``: shape outside the path.  The counts
+    are integer atomics, so this path does not depend on the LDS lane-order self-test (``FAST_PATH_ENABLED`` is not consulted)."""
+    H, W = int(shape[0]), int(shape[1])
+    rng = [(int(lo), int(hi)) for lo, hi in ranges]
+    B = len(rng)
+    if B < 1 or B > _lib.MAX_SEQUENCES:
+        raise ValueError(f"1..{_lib.MAX_SEQUENCES} windows per call")
+    if not want_f32 and not want_u8:
+        raise ValueError("nothing to return: want_f32 or want_u8")
+    n = dat.numel() * dat.element_size() // 8
+    for lo, hi in rng:
+        if lo < 0 or hi < lo or hi > n:
+            raise ValueError(f"record range ({lo}, {hi}) outside 0 <= lo <= hi <= {n}")
+    d, desc = _events_dat(dat, xmap, ymap)
+    need = _lib.load().frlw_eci_batch_workspace_bytes(n, B, H, W)
+    if need == 0:
+        raise NotImplementedError("shape outside the batched Event Count Image path")
+    ws = _slot_workspace(need, d.device, "eci_batch")
+    out = torch.empty((B, 2, H, W), dtype=torch.float32, device=d.device) if want_f32 else None
+    u8 = torch.empty((B, 2, H, W), dtype=torch.uint8, device=d.device) if want_u8 else None
+    rc = _lib.load().frlw_eci_encode_batch(C.byref(desc), (C.c_int64 * B)(*[r[0] for r in rng]), (C.c_int64 * B)(*[r[1] for r in rng]),
+                                           B, H, W, _ptr(out), _ptr(u8), _ptr(ws), ws.numel(), _stream())
+    if rc == _lib.FRLW_ERR_UNSUPPORTED:
+        raise NotImplementedError("input outside the batched Event Count Image path")
+    _lib.check(rc, "encode_eci_batch")
+    if check:
+        _finish(ws, "encode_eci_batch")
+    return out, u8
+
+
+def encode_sae_batch(dat, seq_offsets, shape, lamdas, memory, now, window_us, want_f32=True, want_u8=False, xmap=None, ymap=None,
+                     check=True):
+    """generate_surfaceofactiveevents.py:183-194 for a batch of independent streams in one launch sequence
+    (``frlw_sae_encode_batch``): sequence ``s`` owns the records ``[seq_offsets[s], seq_offsets[s + 1])`` of ``dat``, has its own
+    ``now[s]`` (an int applies to all) and its own plane of ``memory`` ``(B, 2, H, W)`` (``None``: the first call).  Returns
+    ``(f32 (B, 2 * len(lamdas), H, W) or None, u8 or None, new memory (B, 2, H, W))`` -- bit for bit what ``encode_sae_dat`` gives
+    per sequence.  ``ValueError`` outside 1..64 sequences; ``NotImplementedError``: shape outside the path.  ``check`` as for
+    ``encode_eci_batch`` (only the coordinate maps can report an event: one outside the frame is dropped).  Integer atomics: no
+    dependence on the LDS lane-order self-test."""
+    H, W = int(shape[0]), int(shape[1])
+    offs = [int(o) for o in seq_offsets]
+    B = len(offs) - 1
+    if B < 1 or B > _lib.MAX_SEQUENCES:
+        raise ValueError(f"1..{_lib.MAX_SEQUENCES} sequences per call")
+    nows = [int(now)] * B if not hasattr(now, "__len__") else [int(t) for t in now]
+    if len(nows) != B:
+        raise ValueError("one `now` per sequence")
+    if len(lamdas) > _lib.MAX_LAMDAS:
+        raise ValueError(f"at most {_lib.MAX_LAMDAS} lamdas")
+    n = dat.numel() * dat.element_size() // 8
+    if offs[0] < 0 or offs[-1] > n or any(b < a for a, b in zip(offs, offs[1:])):
+        raise ValueError(f"seq_offsets must ascend inside 0..{n}")
+    if memory is not None and tuple(memory.shape) != (B, 2, H, W):
+        raise ValueError(f"memory must be ({B}, 2, {H}, {W})")
+    d, desc = _events_dat(dat, xmap, ymap)
+    need = _lib.load().frlw_sae_batch_workspace_bytes(n, B, H, W)
+    if need == 0:
+        raise NotImplementedError("shape outside the batched Surface of Active Events path")
+    ws = _slot_workspace(need, d.device, "sae_batch")
+    L = len(lamdas)
+    lam = (C.c_double * max(L, 1))(*[float(l) for l in lamdas])
+    out = torch.empty((B, 2 * L, H, W), dtype=torch.float32, device=d.device) if want_f32 else None
+    u8 = torch.empty((B, 2 * L, H, W), dtype=torch.uint8, device=d.device) if want_u8 else None
+    mem_out = torch.empty((B, 2, H, W), dtype=torch.float32, device=d.device)
+    mem_in = None if memory is None else memory.to(torch.float32).contiguous()
+    rc = _lib.load().frlw_sae_encode_batch(C.byref(desc), (C.c_int64 * (B + 1))(*offs), (C.c_int64 * B)(*nows), B, H, W, lam, L,
+                                           _ptr(mem_in), _ptr(mem_out), int(window_us), _ptr(out), _ptr(u8), _ptr(ws), ws.numel(),
+                                           _stream())
+    if rc == _lib.FRLW_ERR_UNSUPPORTED:
+        raise NotImplementedError("input outside the batched Surface of Active Events path")
+    _lib.check(rc, "encode_sae_batch")
+    if check:
+        _finish(ws, "encode_sae_batch")
+    return out, u8, mem_out

@@ -78,11 +78,19 @@ def generate_eventcountimage(raw_dir, label_dir, target_dir, dataset="gen4", dev
     for mode, name, event_file, bbox_file in _sequences(raw_dir, label_dir):
         f_event = dat_io.DatFile(event_file)
         dat = f_event.to_device(device=device)
+        # every (label, window) of the file is a record range of `dat` -- the three windows of a label are nested, they end at the
+        # same record -- so the file's ranges go through the batched encoder, up to 64 per call, instead of one call and one
+        # synchronisation each
+        jobs = []   # (lo, hi, output path)
         for sl in dat_io.eci_label_slices(f_event, read_label_times(bbox_file), events_windows):
             for n in events_windows:
                 lo = max(sl["tail_start"], sl["end_count"] - n)
-                _, u8 = er.encode_eci_dat(dat[lo:sl["end_count"]], enc, want_f32=False, want_u8=True, xmap=xmap, ymap=ymap)
-                _write(u8, enc, target, os.path.join(target_dir, f"EventCountImage{n}", mode, f"{name}_{sl['label_time']}.npy"))
+                jobs.append((lo, sl["end_count"], os.path.join(target_dir, f"EventCountImage{n}", mode, f"{name}_{sl['label_time']}.npy")))
+        for j0 in range(0, len(jobs), er._lib.MAX_SEQUENCES):
+            part = jobs[j0:j0 + er._lib.MAX_SEQUENCES]
+            _, u8 = er.encode_eci_batch(dat, [(lo, hi) for lo, hi, _ in part], enc, want_f32=False, want_u8=True, xmap=xmap, ymap=ymap)
+            for b, (_, _, path) in enumerate(part):
+                _write(u8[b], enc, target, path)
                 n_files += 1
     return n_files
 
@@ -94,6 +102,8 @@ def generate_eventvolume(raw_dir, label_dir, target_dir, dataset="gen1", device=
     _, target, enc, xmap, ymap = _geometry(dataset, device)
     os.makedirs(target_dir, exist_ok=True)
     n_files = 0
+    # (one call per label window: the label slices of a file overlap, which encode_ev_batch's contiguous partition of the record
+    # array cannot express)
     for mode, name, event_file, bbox_file in _sequences(raw_dir, label_dir):
         f_event = dat_io.DatFile(event_file)
         dat = f_event.to_device(device=device)
@@ -117,7 +127,8 @@ def generate_surfaceofactiveevents(raw_dir, label_dir, target_dir, dataset="gen1
     for mode, name, event_file, bbox_file in _sequences(raw_dir, label_dir):
         f_event = dat_io.DatFile(event_file)
         dat = f_event.to_device(device=device)
-        memory = None
+        memory = None   # carried from label to label within a file: the labels are a chain, not a batch (encode_sae_batch is for
+        # independent streams), so this loop stays one call per label
         for sl in dat_io.sae_label_slices(f_event, read_label_times(bbox_file)):
             rec = dat[sl["start_count"]:sl["end_count"]]
             # the test split runs all three windows, each on the memory the previous one left (:178-194); the file holds the

@@ -247,6 +247,42 @@ int frlw_ev_encode_batch(const frlw_events_t *ev, const int64_t *seq_offsets, co
                          int bins, int64_t window_us, float *out_f32, uint8_t *out_u8, void *workspace,
                          size_t workspace_bytes, frlw_stream_t stream);
 
+/*
+ * Event Count Image for a batch of record windows (csrc/encoders_batch.hip) -- generate_eventframe
+ * (generate_eventcountimage.py:19-41) for n_win <= FRLW_MAX_SEQUENCES windows in one launch sequence.  Window w is the DAT8
+ * records [win_lo[w], win_hi[w]) of ev->data (HOST arrays of record indices); windows may overlap, nest (the offline command's
+ * three windows per label end at the same record) or be empty.  out_f32 and / or out_u8: (n_win, 2, H, W).
+ * Bit-identical to n_win calls of frlw_eci_encode on the same record ranges, coordinate maps included.  DAT8 only; an event whose
+ * flat pixel lies outside the frame is reported by frlw_encoder_status() as FRLW_ERR_INDEX (the outputs are then unspecified).
+ * The counts are integer atomics on a (n_win, 2, H, W) plane of the workspace: exact in any order, no dependence on the LDS
+ * lane-order self-test.  Workspace: frlw_eci_batch_workspace_bytes(total records, n_win, H, W); 0 = n_win outside
+ * 1..FRLW_MAX_SEQUENCES or an unsupported shape.  More windows than that, or a range running backwards / outside the array:
+ * FRLW_ERR_ARG.
+ */
+size_t frlw_eci_batch_workspace_bytes(int64_t n_records, int n_win, int H, int W);
+int frlw_eci_encode_batch(const frlw_events_t *ev, const int64_t *win_lo, const int64_t *win_hi, int n_win, int H, int W,
+                          float *out_f32, uint8_t *out_u8, void *workspace, size_t workspace_bytes, frlw_stream_t stream);
+
+/*
+ * Surface of Active Events for a batch of independent streams (csrc/encoders_batch.hip) -- generate_leaky_cuda and its harness
+ * lines (generate_surfaceofactiveevents.py:44-80, :183) for n_seq <= FRLW_MAX_SEQUENCES streams in one launch sequence.  Sequence
+ * s owns the DAT8 records [seq_offsets[s], seq_offsets[s + 1]) (HOST array of n_seq + 1 record indices), has its own now[s] (HOST
+ * array) and its own memory plane: mem_in (or NULL = no memory yet, as for frlw_sae_encode) and mem_out are (n_seq, 2, H, W) and
+ * may alias; out_f32 / out_u8 (both optional): (n_seq, 2 * n_lamda, H, W).  Bit-identical to n_seq calls of frlw_sae_encode --
+ * memory, f32 and u8: events outside the frame are dropped, events with t <= now[s] - window_us are dropped (window_us <= 0
+ * keeps all), a cell keeps its LAST event in stream order, cells without one start from now[s] - 5e6.  DAT8 only.
+ * Workspace: frlw_sae_batch_workspace_bytes(total records, n_seq, H, W); 0 = n_seq outside 1..FRLW_MAX_SEQUENCES or an
+ * unsupported shape.
+ */
+size_t frlw_sae_batch_workspace_bytes(int64_t n_records, int n_seq, int H, int W);
+int frlw_sae_encode_batch(const frlw_events_t *ev, const int64_t *seq_offsets, const int64_t *now, int n_seq, int H, int W,
+                          const double *lamdas, int n_lamda, const float *mem_in, float *mem_out, int64_t window_us,
+                          float *out_f32, uint8_t *out_u8, void *workspace, size_t workspace_bytes, frlw_stream_t stream);
+
+/* Calls served by the two entry points above, counted per process since it loaded the library: counts[0] =
+ * frlw_eci_encode_batch, counts[1] = frlw_sae_encode_batch (host-side: ENQUEUES, the replays of a captured graph add nothing). */
+int frlw_encoder_batch_counts(uint64_t counts[2]);
+
 /* The verdict of the one-time LDS lane-order self-test of the fast paths (frlw_taf_encode_batch, frlw_ev_encode_batch, the
  * two-launch forms of frlw_sae_encode / frlw_eci_encode) for the CURRENT device: *ok_out = 1 when the property held, 0 when
  * it did not (those entry points then answer FRLW_ERR_UNSUPPORTED and callers take the general path -- same bits, different

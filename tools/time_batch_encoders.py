@@ -1,0 +1,155 @@
+#!/usr/bin/env python3
+"""Timings of the batched Event Count Image / Surface of Active Events encoders against the single calls they replace, same
+box, same run, one JSON line each:
+
+  eci   64 windows x 100 000 events at 304x240: one encode_eci_batch against 64 encode_eci_dat calls
+  sae   64 streams x 1 000 000 events, 3 lamdas:  one encode_sae_batch against 64 encode_sae_dat calls
+
+Device events around `n` back-to-back repetitions, `--runs` (>= 5) such regions after a warm-up; the value is the median, the
+spread min .. max.  Both sides are timed unchecked (``check=False``: no host synchronisation, the device's best case for the
+single calls) and checked (their default).  GB/s = 8 bytes per record plus the planes written (and the memory read), over the
+batched call's time.  Each side runs in a child process of its own under a time limit; the parent never opens the GPU and
+starts nothing more after a child that did not end normally.
+
+``python tools/time_batch_encoders.py [--runs 7] [--out profiles/eci_sae_batch_time.txt]``
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+H, W, B = 240, 304, 64
+LAMDAS = [0.00001, 0.0000025, 0.000001]
+LIMIT_S = {"eci": 240, "sae": 420}
+
+
+def regions(fn, runs, n, warm=2):
+    import torch
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(runs):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(n):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        out.append(e0.elapsed_time(e1) / n)
+    return out
+
+
+def report(name, ms, **extra):
+    import numpy as np
+    row = {"what": name, "ms_median": round(float(np.median(ms)), 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4),
+           "runs": len(ms)}
+    row.update(extra)
+    print(json.dumps(row), flush=True)
+    return float(np.median(ms))
+
+
+def streams(n_distinct, n, seed, t_offset=0):
+    """B streams of n events back to back (n_distinct different ones, repeated) as one (B * n, 8) uint8 device tensor."""
+    import numpy as np
+    import torch
+    from frlw_evd_amd import synth
+    parts = [synth.to_dat8(synth.synth_events(seed + k, n, W, H, 1_000_000, hotspot=bool(k & 1), t_offset=t_offset)) for k in range(n_distinct)]
+    rec = np.concatenate([parts[s % n_distinct] for s in range(B)])
+    return torch.from_numpy(rec.view(np.uint8).reshape(-1, 8).copy()).cuda()
+
+
+def side_eci(runs):
+    import torch
+    from frlw_evd_amd import event_representation as er
+    n = 100_000
+    dat = streams(16, n, 100)
+    ranges = [(s * n, (s + 1) * n) for s in range(B)]
+    parts = [dat[lo:hi] for lo, hi in ranges]
+    f32, _ = er.encode_eci_batch(dat, ranges, (H, W))
+    assert all(torch.equal(f32[s], er.encode_eci_dat(parts[s], (H, W))[0]) for s in range(B))
+    nbytes = B * n * 8 + B * 2 * H * W * 4
+    res = {}
+    for check in (False, True):
+        tag = "checked" if check else "unchecked"
+        res["b", check] = report(f"eci batch: 1 call, {B} windows x {n} events, {tag}",
+                                 regions(lambda: er.encode_eci_batch(dat, ranges, (H, W), check=check), runs, 10))
+        res["s", check] = report(f"eci single: {B} calls x {n} events, {tag}",
+                                 regions(lambda: [er.encode_eci_dat(p, (H, W), check=check) for p in parts], runs, 3))
+        er.raise_deferred()
+    print(json.dumps({"what": "eci: batched / 64 single calls", "ratio_unchecked": round(res["b", False] / res["s", False], 4),
+                      "ratio_checked": round(res["b", True] / res["s", True], 4), "bytes": nbytes,
+                      "batched_GB_per_s": round(nbytes / res["b", False] / 1e6, 1),
+                      "us_per_window_batched": round(res["b", False] * 1e3 / B, 2), "us_per_single_call": round(res["s", False] * 1e3 / B, 2)}),
+          flush=True)
+
+
+def side_sae(runs):
+    import torch
+    from frlw_evd_amd import event_representation as er
+    n = 1_000_000
+    now, win = 11_000_500, 800_000
+    dat = streams(8, n, 200, t_offset=10_000_000)
+    offs = [s * n for s in range(B + 1)]
+    parts = [dat[offs[s]:offs[s + 1]] for s in range(B)]
+    mem = torch.full((B, 2, H, W), 9_000_000.0, device="cuda")
+    f32, _, m = er.encode_sae_batch(dat, offs, (H, W), LAMDAS, mem, now, win)
+    for s in (0, 1, B - 1):
+        f1, _, m1 = er.encode_sae_dat(parts[s], (H, W), LAMDAS, mem[s], now, win)
+        assert torch.equal(f32[s], f1) and torch.equal(m[s], m1)
+    nbytes = B * n * 8 + B * 2 * H * W * 4 * (2 + len(LAMDAS))   # records, memory in and out, the f32 decays
+    res = {}
+    for check in (False, True):
+        tag = "checked" if check else "unchecked"
+        res["b", check] = report(f"sae batch: 1 call, {B} streams x {n} events, {tag}",
+                                 regions(lambda: er.encode_sae_batch(dat, offs, (H, W), LAMDAS, mem, now, win, check=check), runs, 3))
+        res["s", check] = report(f"sae single: {B} calls x {n} events, {tag}",
+                                 regions(lambda: [er.encode_sae_dat(parts[s], (H, W), LAMDAS, mem[s], now, win, check=check)
+                                                  for s in range(B)], runs, 2))
+        er.raise_deferred()
+    print(json.dumps({"what": "sae: batched / 64 single calls", "ratio_unchecked": round(res["b", False] / res["s", False], 4),
+                      "ratio_checked": round(res["b", True] / res["s", True], 4), "bytes": nbytes,
+                      "batched_GB_per_s": round(nbytes / res["b", False] / 1e6, 1),
+                      "us_per_stream_batched": round(res["b", False] * 1e3 / B, 2), "us_per_single_call": round(res["s", False] * 1e3 / B, 2)}),
+          flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", type=int, default=7)
+    ap.add_argument("--only", choices=("eci", "sae"))
+    ap.add_argument("--out")
+    a = ap.parse_args()
+    assert a.runs >= 5
+    if a.only:
+        import torch
+        from frlw_evd_amd import _lib
+        print(json.dumps({"device": torch.cuda.get_device_name(0), "library": _lib.load().frlw_version().decode(), "side": a.only}), flush=True)
+        {"eci": side_eci, "sae": side_sae}[a.only](a.runs)
+        return 0
+    text = ""
+    for side in ("eci", "sae"):
+        try:
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--only", side, "--runs", str(a.runs)], capture_output=True,
+                               text=True, timeout=LIMIT_S[side])
+        except subprocess.TimeoutExpired:
+            print(f"{side}: no result inside {LIMIT_S[side]} s; nothing more is started", file=sys.stderr)
+            return 1
+        sys.stdout.write(p.stdout)
+        text += p.stdout
+        if p.returncode != 0:
+            sys.stderr.write(p.stderr[-3000:])
+            print(f"{side}: exit status {p.returncode}; nothing more is started", file=sys.stderr)
+            return 1
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(text)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
