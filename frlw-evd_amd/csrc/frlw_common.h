@@ -7,11 +7,10 @@
 #include <stdlib.h>
 #include <atomic>
 
+#include "frlw_consts.h" // kWave, kMaxBpw, kHeaderBytes
 #include "frlw_evd.h"
 
 namespace frlw {
-
-constexpr int kWave = 64;
 
 // Inclusive prefix sum over the 64 lanes of a wavefront in the vector ALU (DPP row shifts inside the rows of 16 lanes, then
 // the row totals by row_bcast15 / row_bcast31): six adds, no LDS crossbar round trips (a __shfl_up scan is six dependent
@@ -51,7 +50,6 @@ constexpr int kMaxTiles = 2048;   // LDS of the scatter workgroup: 52 B per tile
 constexpr int kMaxTlut = 1 << 16; // longest TAF window (us) served by the value table
 constexpr int kPartThreads = 1024; // partition workgroup = 16 wavefronts
 constexpr int kPartWaves = kPartThreads / kWave;
-constexpr int kMaxBpw = 8;        // batches of 64 events per wavefront per workgroup chunk (registers!)
 constexpr int kSlabUnits = 32;    // workgroups per slab of the two-level column scan
 
 enum Kind : int { KIND_ECI = 0, KIND_EV = 1, KIND_SAE = 2, KIND_TAF = 3 };
@@ -68,7 +66,6 @@ struct WsHeader {
     uint32_t hot_thr;
     uint32_t hot[kMaxHot];
 };
-constexpr size_t kHeaderBytes = 1024;
 static_assert(sizeof(WsHeader) <= kHeaderBytes, "header");
 // Two words at the end of the header outlive the per-call reset: `sticky` is the OR of the status of every encoder call
 // since frlw_workspace_init / the last frlw_encoder_deferred_status (unchecked callers read it once per batch or epoch

@@ -594,3 +594,33 @@ def test_workspace_of_exactly_the_queried_size_gets_the_two_launch_form(er, kind
     _lib.check(lib.frlw_encoder_status(C.c_void_p(ws.data_ptr()), st, C.byref(status)), "status")
     assert status.value == 0
     assert torch.equal(out, want)
+
+
+@pytest.mark.parametrize("kind", ["sae", "eci"])
+def test_two_launch_form_at_its_floor_with_long_runs_and_empty_sub_tiles(er, kind, monkeypatch):
+    """kf_sae_sub (both forms) at the eligibility floor, 16 384 events at 304x240 = 16 chunks of 1024: a quarter of the events in
+    one 8x8 block (it spans four sub-tiles: each one's runs hold some 50 to 64 records, the tail loop behind a run's first 16), rows 0 and 1 without any event
+    (sub-tile 0 of the top tiles: an empty column, L[C] = 0) -- the two-launch form, by the path counter, against the general path
+    (the tuning knob), bit for bit."""
+    from frlw_evd_amd import _lib
+    H, W, n = 240, 304, 16384
+    ev = synth.synth_events(7600, n, W, H, 5_000_000, t_offset=33_500_000)
+    k = np.arange(len(ev["x"][::4]))
+    ev["x"][::4] = 100 + k % 8
+    ev["y"][::4] = 60 + (k // 8) % 8
+    ev["y"][ev["y"] < 2] = 2
+    dat = dat_dev(ev)
+    res = []
+    for tun in (None, _lib.FrlwTuning(staged_scatter=0)):
+        monkeypatch.setattr(er, "TUNING", tun)
+        c0 = path_counts()
+        if kind == "sae":
+            res.append(er.encode_sae_dat(dat, (H, W), LAMDAS, None, 40_000_000, 5_541_263, want_u8=True))
+            want = [1, 0, 0, 0] if tun is None else [0, 1, 0, 0]
+        else:
+            res.append(er.encode_eci_dat(dat, (H, W), want_u8=True))
+            want = [0, 0, 1, 0] if tun is None else [0, 0, 0, 1]
+        assert list(path_counts() - c0) == want, tun
+    monkeypatch.setattr(er, "TUNING", None)
+    for a, b in zip(res[0], res[1]):
+        assert torch.equal(a, b)

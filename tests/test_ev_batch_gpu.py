@@ -185,3 +185,53 @@ def test_single_window_shim_takes_the_two_launch_path(er, orc):
     late["t"][-2:] += 7  # behind t_end: outside the batch path's contract
     out, _ = er.encode_ev_dat(to_dev(late), (H, W), win, win, 5, fast=True)
     assert_bitexact(host(out), orc.ev_stream_dat8(late, (H, W), (H, W), 5, win, win), "late events through the fall-back")
+
+
+@pytest.fixture(scope="module")
+def gather_inputs():
+    """(a) one window whose hottest sub-tile list (a quarter of 300 000 events in one 8x8 block) is far above the 2048 records a
+    consumer keeps in LDS: the list goes through rec2[] at the header's cursor, and its runs are longer than 16 records;
+    (b) one window of 2.1 M events: direct-mode chunks at 304x240 hold about 6 000 events (the scatter's LDS cap), so a column has
+    well over 300 chunks -- two passes of kf_ev_fadd's 256-thread loader, six steps of kf_ev_sub's 64-lane one -- and stays below the
+    511 a consumer's column holds."""
+    H, W, win = 240, 304, 100_000
+    out = {}
+    for name, n in (("long_list", 300_000), ("two_pass_column", 2_100_000)):
+        ev = synth.synth_events(9100 + n % 7, n, W, H, win, t_offset=1)
+        if name == "long_list":
+            k = np.arange(len(ev["x"][::4]))
+            ev["x"][::4] = 200 + k % 8
+            ev["y"][::4] = 100 + (k // 8) % 8
+        out[name] = synth.to_dat8(ev)
+    return out
+
+
+@pytest.mark.parametrize("bins", [5, 8])
+@pytest.mark.parametrize("case", ["long_list", "two_pass_column", "empty_second"])
+def test_chunk_major_direct_consumers_gather_long_lists_and_long_columns(er, gather_inputs, case, bins, monkeypatch):
+    """kf_ev_fadd and kf_ev_sub<., true> (``ev_lds_float_atomics`` 1 / 0 with ``direct_bins`` = ``chunk_major`` = 1: each gathers
+    its sub-tile's list from the chunk-major directory) against each other and the general path, bit for bit, on the inputs of
+    ``gather_inputs``; ``empty_second``: a batch whose second sequence is empty (a column of one empty chunk)."""
+    import ctypes as C
+    from frlw_evd_amd import _lib
+    # kf_ev_fadd is launched only where the library's self-test saw ds_add_f32 make the sequential sums (else both knob values
+    # run kf_ev_sub<., true> and the comparison below says nothing about it): the same self-test, same size, must say so here
+    st_out = torch.zeros(3, dtype=torch.int64, device="cuda")
+    _lib.check(_lib.load().frlw_selftest_lds_atomic_order(40, 64, C.c_void_p(st_out.data_ptr()),
+                                                          C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    bad, conflicts, fbad = (int(v) for v in st_out.cpu())
+    assert conflicts > 0 and bad == 0 and fbad == 0, (bad, conflicts, fbad)
+    H, W, win = 240, 304, 100_000
+    rec = gather_inputs["long_list" if case == "empty_second" else case]
+    offs = [0, len(rec), len(rec)] if case == "empty_second" else [0, len(rec)]
+    dat = to_dev(rec)
+    outs = []
+    for knob in (1, 0):
+        monkeypatch.setattr(er, "TUNING", _lib.FrlwTuning(ev_lds_float_atomics=knob, direct_bins=1, chunk_major=1))
+        outs.append(er.encode_ev_batch(dat, offs, (H, W), win, win, bins, want_u8=True))
+    monkeypatch.setattr(er, "TUNING", None)
+    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+    want, want_u8 = er.encode_ev_dat(dat, (H, W), win, win, bins, want_u8=True, fast=False)  # the general path
+    assert torch.equal(outs[0][0][0], want) and torch.equal(outs[0][1][0], want_u8)
+    if case == "empty_second":
+        assert float(outs[0][0][1].abs().sum()) == 0.0
