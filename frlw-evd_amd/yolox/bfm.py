@@ -9,7 +9,7 @@ Dropout2d layers are identities in eval mode), then the usual Focus space-to-dep
 
 Parameter names equal the reference's (``convs.{i}.weight_g / weight_v / bias`` from the old-style
 ``nn.utils.weight_norm``, ``trans_up``, ``trans_down``, ``conv.conv`` / ``conv.bn``).  On a ROCm device in eval
-mode the whole per-pixel part runs as ONE fused kernel of the detector plan (csrc/detector.hip, k_bfm_stem).
+mode the whole per-pixel part runs as ONE fused kernel of the detector plan (csrc/det_bfm.h, k_bfm_stem).
 """
 import warnings
 from math import log2
