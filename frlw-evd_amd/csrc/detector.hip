@@ -182,7 +182,7 @@ int frlw_det_set_scratch(frlw_detector_t *d, int buf, int64_t n_floats)
 
 int frlw_det_add_focus(frlw_detector_t *d, int src_buf, int C, int H, int W, int dst_buf)
 {
-    if (!d || C < 1 || (H & 1) || (W & 1)) return FRLW_ERR_ARG;
+    if (!d || C < 1 || H < 1 || W < 1 || (H & 1) || (W & 1)) return FRLW_ERR_ARG;
     Op op = {};
     op.focus = FocusOp{src_buf, dst_buf, C, H, W};
     return d->add(OP_FOCUS, d->cur_lane, op);
@@ -225,7 +225,7 @@ int frlw_det_bfm_weight_count(int C) { return bfm_weight_count(C); }
 
 int frlw_det_add_bfm_stem(frlw_detector_t *d, int src_buf, int C, int H, int W, const float *weights, int n_weights, int dst_buf)
 {
-    if (!d || !weights || (H & 1) || (W & 1)) return FRLW_ERR_ARG;
+    if (!d || !weights || C < 1 || H < 1 || W < 1 || (H & 1) || (W & 1)) return FRLW_ERR_ARG;
     const int want = bfm_weight_count(C);
     if (want == 0) return FRLW_ERR_UNSUPPORTED; // TAF with K = 2, 4 or 8 FIFO slots
     if (n_weights != want) return FRLW_ERR_ARG;
@@ -237,7 +237,7 @@ int frlw_det_add_bfm_stem(frlw_detector_t *d, int src_buf, int C, int H, int W, 
 int frlw_det_add_upsample(frlw_detector_t *d, int src_buf, int cs_src, int co_src, int C, int H, int W,
                           int dst_buf, int cs_dst, int co_dst)
 {
-    if (!d) return FRLW_ERR_ARG;
+    if (!d || C < 1 || H < 1 || W < 1) return FRLW_ERR_ARG;
     if (!d->ops.empty() && d->ops.back().type == OP_CONV) {
         // the slice was written by the convolution added just before (the FPN's lateral / reduce 1x1, yolo_pafpn.py:92-100): its
         // epilogue stores the upsampled copy as well -- four more 16-byte stores per output row instead of a launch
@@ -257,7 +257,7 @@ int frlw_det_add_upsample(frlw_detector_t *d, int src_buf, int cs_src, int co_sr
 
 int frlw_det_add_spp_pool(frlw_detector_t *d, int buf, int cs, int C, int H, int W)
 {
-    if (!d || cs < 4 * C) return FRLW_ERR_ARG;
+    if (!d || C < 1 || H < 1 || W < 1 || cs < 4 * C) return FRLW_ERR_ARG;
     if (H * W > kSppMaxPix) return FRLW_ERR_UNSUPPORTED;
     Op op = {};
     op.spp = SppOp{buf, C, H, W, cs};
@@ -331,9 +331,13 @@ int frlw_det_run(const frlw_detector_t *d, int B, void *const *bufs, int n_bufs,
         }
         const hipStream_t s = (op.lane > 0 && d->have_side) ? d->side[op.lane - 1] : s0;
         switch (op.type) {
-        case OP_FOCUS:
-            if (!launch_focus(buf(op.focus.src), B, op.focus.C, op.focus.H, op.focus.W, buf(op.focus.dst), s)) return FRLW_ERR_UNSUPPORTED;
+        case OP_FOCUS: {
+            const float *x = buf(op.focus.src);
+            float *y = buf(op.focus.dst);
+            if (!x || !y) return FRLW_ERR_ARG;
+            if (!launch_focus(x, B, op.focus.C, op.focus.H, op.focus.W, y, s)) return FRLW_ERR_UNSUPPORTED;
             break;
+        }
         case OP_FOCUS_STEM: {
             FocusStemArgs a = op.fstem.a;
             a.x = buf(op.fstem.src); a.y = buf(op.fstem.dst);
@@ -341,9 +345,26 @@ int frlw_det_run(const frlw_detector_t *d, int B, void *const *bufs, int n_bufs,
             launch_focus_stem(a, op.fstem.plan, B, s);
             break;
         }
-        case OP_BFM: launch_bfm_stem(op.bfm, buf(op.bfm.src), buf(op.bfm.dst), B, s); break;
-        case OP_UPSAMPLE: launch_upsample2x(op.ups, buf(op.ups.src), buf(op.ups.dst), B, s); break;
-        case OP_SPP: launch_spp_pool(op.spp, buf(op.spp.buf), B, s); break;
+        case OP_BFM: {
+            const float *x = buf(op.bfm.src);
+            float *y = buf(op.bfm.dst);
+            if (!x || !y) return FRLW_ERR_ARG;
+            launch_bfm_stem(op.bfm, x, y, B, s);
+            break;
+        }
+        case OP_UPSAMPLE: {
+            const float *x = buf(op.ups.src);
+            float *y = buf(op.ups.dst);
+            if (!x || !y) return FRLW_ERR_ARG;
+            launch_upsample2x(op.ups, x, y, B, s);
+            break;
+        }
+        case OP_SPP: {
+            float *io = buf(op.spp.buf);
+            if (!io) return FRLW_ERR_ARG;
+            launch_spp_pool(op.spp, io, B, s);
+            break;
+        }
         case OP_CONV: {
             ConvArgs c = op.conv.a;
             c.x = buf(op.conv.src); c.y = buf(op.conv.dst); c.res = buf(op.conv.res);

@@ -442,7 +442,9 @@ int frlw_det_add_decode_nms(frlw_detector_t *d, int raw_buf, int A, int nc, int 
                             const int *lvl_w, const int *lvl_stride, float obj_thr, float iou_thr,
                             int decoded_buf, int dets_buf, int counts_buf, int nms_buf);
 
-/* Launch ops [first, last) (last < 0: to the end) for B images on `stream`; bufs: n_bufs device pointers. */
+/* Launch ops [first, last) (last < 0: to the end) for B images on `stream`; bufs: n_bufs device pointers.  An op of any kind
+ * whose buffer index lies outside the table or holds NULL ends the run with FRLW_ERR_ARG before that op launches anything
+ * (the optional ones excepted: a convolution's residual, the decoded boxes). */
 int frlw_det_run(const frlw_detector_t *d, int B, void *const *bufs, int n_bufs, int first, int last,
                  frlw_stream_t stream);
 
