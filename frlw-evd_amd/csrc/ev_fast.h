@@ -243,7 +243,8 @@ __global__ __launch_bounds__(4 * kWave) __attribute__((amdgpu_waves_per_eu((BINS
     __shared__ uint32_t s_list[CMD ? 4 : 1][CMD ? kEvListCap : 1];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     if (lane < 2) s_sorted[wv][2 * kSubCells + lane] = 0.0f; // the all-zero pair behind the segments
-    const int sg = blockIdx.x * 4 + wv;
+    // (CMD: the workgroup's four bins through the XCD mapping -- the runs of neighbouring bins share cache lines of rec[])
+    const int sg = (CMD ? (int)xcd_owned_index(blockIdx.x, gridDim.x) : (int)blockIdx.x) * 4 + wv;
     if (sg >= q.pairs * kFW || q.hdr->status != 0) return;
     const int g = sg / kFW, sub = sg - g * kFW;
     const int s = g / q.T, tile = g - s * q.T;
@@ -350,7 +351,7 @@ __global__ __launch_bounds__(kFaddWaves *kWave) void kf_ev_fadd(EvTileP q, CmP c
     __shared__ uint32_t s_colL[kColEv + 1], s_colD[kColEv], s_wsum[kFaddWaves + 1];
     __shared__ uint32_t s_list[kEvListCap];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int sg = blockIdx.x;
+    const int sg = (int)xcd_owned_index(blockIdx.x, gridDim.x); // (neighbouring bins, whose runs share cache lines of rec[], through one L2)
     if (sg >= q.pairs * kFW || q.hdr->status != 0) return;
     const int g = sg / kFW, sub = sg - g * kFW;
     const int s = g / q.T, tile = g - s * q.T;

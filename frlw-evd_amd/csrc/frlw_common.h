@@ -9,6 +9,7 @@
 
 #include "frlw_consts.h" // kWave, kMaxBpw, kHeaderBytes
 #include "frlw_evd.h"
+#include "xcd_map.h"
 
 namespace frlw {
 
@@ -203,19 +204,7 @@ __device__ __forceinline__ float f64_value(double t)
     return (float)t;
 }
 
-// Workgroups are handed to the 8 XCDs round-robin (block b runs on XCD b % 8) and every XCD has its own L2.  Chunk
-// c of the stream is therefore given to block (c - start_k) * 8 + k with k the XCD that owns the contiguous chunk range
-// [start_k, start_{k+1}): consecutive chunks -- whose runs are neighbours in every tile's record list -- are written
-// through the SAME L2, which merges the lines they share before they reach the HBM.
-__device__ __forceinline__ long long chunk_of_block(unsigned block, unsigned n_blocks)
-{
-#ifdef FRLW_NO_XCD_REMAP
-    return block;
-#else
-    const unsigned k = block & 7u, idx = block >> 3, q = n_blocks >> 3, r = n_blocks & 7u;
-    return (long long)k * q + (k < r ? k : r) + idx;
-#endif
-}
+// chunk_of_block / xcd_owned_index: xcd_map.h (which chunk a scatter workgroup writes, which bin a consumer workgroup reads)
 
 __device__ __forceinline__ uint64_t lanemask_lt()
 {

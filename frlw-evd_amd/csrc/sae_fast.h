@@ -31,7 +31,8 @@ __global__ __launch_bounds__(kSubCells) void kf_sae_sub(SaeFastP q, CmP cm, SeqT
     __shared__ uint32_t s_colL[kColEv + 1], s_colD[kColEv], s_wsum[kSubCells / kWave + 1];
     constexpr int NT = kSubCells;
     const int tid = threadIdx.x;
-    const int sg = blockIdx.x, tile = sg / kFW, sub = sg - tile * kFW; // (one sequence)
+    // (the bin through the XCD mapping: the runs of neighbouring bins share cache lines of rec[])
+    const int sg = (int)xcd_owned_index(blockIdx.x, gridDim.x), tile = sg / kFW, sub = sg - tile * kFW; // (one sequence)
     if (q.hdr->status != 0) return;
     s_last[tid] = 0u;
     const int C = S.chunk0[1] - S.chunk0[0]; // (<= kColEv)

@@ -133,7 +133,10 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         }
         return;
     }
-    const int g = blk;
+    // CM: the tile comes from the XCD mapping -- tiles g and g + 1 share the cache lines at the ends of their runs in every
+    // chunk's stretch of rec[] (a run is ~43 records at an arbitrary offset on the headline: 2.3 lines for 1.3 lines' worth of
+    // records), and neighbouring BLOCKS sit on different L2s.  Everything below is keyed by g, never by the block.
+    const int g = CM ? (int)xcd_owned_index(blockIdx.x, gridDim.x) : blk;
     uint32_t beg, n;
     uint32_t m[kWholeChunks][RPT];
     if (CM) {
@@ -533,6 +536,8 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     if (q.hdr->status != 0) return;
     uint32_t nseg = CM ? q.hdr->seg_cursor : q.seg0[q.pairs];
     if (CM && nseg > (uint32_t)cm.max_segs) nseg = (uint32_t)cm.max_segs;
+    // (the segment from the block index, NOT through xcd_owned_index: a skewed call has fewer segments than workgroups (a few hundred of 512 with a
+    // quarter of 10 M events in one blob), and the mapping would hand them all to the first XCDs and leave the others idle)
     for (uint32_t seg = blockIdx.x; seg < nseg; seg += gridDim.x) { // (workgroup-uniform: most calls have no segment at all)
         split_place_segment<CM>(q, seg, L, cm, S, cl);
         __syncthreads(); // the LDS image is reused
@@ -550,7 +555,7 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     if (q.hdr->status != 0) return;
     uint32_t nseg = q.hdr->seg_cursor;
     if (nseg > (uint32_t)cm.max_segs) nseg = (uint32_t)cm.max_segs;
-    for (uint32_t seg = blockIdx.x; seg < nseg; seg += gridDim.x) {
+    for (uint32_t seg = blockIdx.x; seg < nseg; seg += gridDim.x) { // (not through xcd_owned_index: see kf_split_place)
         const int g = __builtin_amdgcn_readfirstlane((int)cm.segdesc[seg]), s = g / q.T;
         const uint32_t n = col_load<kFT>(cm, S, s, g - s * q.T, cl.L, cl.D, cl.wsum);
         const uint32_t beg = (seg - (uint32_t)__builtin_amdgcn_readfirstlane((int)cm.hot_seg0[g])) * (uint32_t)kSplitSeg;

@@ -84,7 +84,10 @@ __global__ __launch_bounds__(kWalkThreads) __attribute__((amdgpu_waves_per_eu(8,
     __shared__ int s_unsorted;
     __shared__ __attribute__((aligned(16))) uint32_t s_list[CMD ? kWalkListCap : 4]; // CMD: the gathered list, when it fits (else it goes to rec2[])
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int sg = blockIdx.x, g = sg / kFW, sub = sg - g * kFW;
+    // CMD: the sub-tile comes from the XCD mapping -- the short runs of neighbouring bins (a dozen records, several to a cache line,
+    // in every chunk's stretch of rec[]) go through one L2.  The other forms read whole lists, which share next to nothing with
+    // their neighbours (measured: same time), and keep the block index: the heavy sub-tiles of a hot spot stay spread over the XCDs.
+    const int sg = CMD ? (int)xcd_owned_index(blockIdx.x, gridDim.x) : (int)blockIdx.x, g = sg / kFW, sub = sg - g * kFW;
     const int s = g / q.T, tile = g - s * q.T;
     // Everything the workgroup needs from the header and the list tables is requested in ONE go, in front of the status test:
     // each of these is a scalar load of its own round trip, and one behind a branch waits for the one in front of it.  (The
