@@ -3,14 +3,14 @@
 //
 // Both encodings are order-free per cell: the count image depends on the number of events of a cell, saturating at
 // 20 (generate_eventcountimage.py:32-34), the surface on the LAST event of a cell in stream order
-// (generate_surfaceofactiveevents.py:49).  So neither needs the partition of encoders.hip / taf_fast.hip nor the LDS lane-order
+// (generate_surfaceofactiveevents.py:49).  So neither needs the partition of partition.hip / taf_fast.hip nor the LDS lane-order
 // property the batched TAF / Event Volume paths rest on: every record goes straight from the raw DAT array to an integer atomic on
 // a per-window plane in the workspace -- exact in any arrival order -- and an element-wise kernel turns the planes into the outputs:
 //
 //   kb_zero        planes <- 0, the call's status word <- 0
 //   kb_eci_count   (window, slice of 4096 records): cnt[w][p][y][x] += 1     (skipped once the cell reads >= 20: it is saturated)
-//   kb_eci_out     cnt -> the 21-entry table of frlw_eci_encode -> f32 / u8 (the plane already has the (2, H, W) layout)
-//   kb_sae_last    (sequence, slice): last[s][p][y][x] = max(last, (position + 1) << 32 | bits(float(t)))  -- the key of k_sae_tile,
+//   kb_eci_out     cnt -> the 21-entry table of frlw_eci_encode (eci_lut, enc_plan.h) -> f32 / u8 (the plane already has the (2, H, W) layout)
+//   kb_sae_last    (sequence, slice): last[s][p][y][x] = max(last, (position + 1) << 32 | bits(float(t)))  -- the key of k_sae_tile (enc_sae.h),
 //                  so an unsorted stream gives the same last writer as frlw_sae_encode; the slices of a sequence are handed out
 //                  back to front and a lane whose key is already beaten skips its atomic (only ~one atomic per touched cell is left)
 //   kb_sae_out     key -> float(t) or the floor, torch.where against the carried memory, the n_lamda decays
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(kBT) void kb_sae_last(BatchDecode D, BatchTab T, in
             ok = ok && x < D.W && y < D.H;                         // generate_surfaceofactiveevents.py:72: dropped, no error
             if (time_filter) ok = ok && (long long)r[u].x > t0;    // :183
             cell[u] = ok ? p * total + (long long)y * D.W + x : -1;
-            // last writer in stream order = max over (position in the sequence + 1, bits of float(t)): the key of k_sae_tile
+            // last writer in stream order = max over (position in the sequence + 1, bits of float(t)): the key of k_sae_tile (enc_sae.h)
             key[u] = ((unsigned long long)(i - first + 1) << 32) | __float_as_uint((float)r[u].x);
             seen[u] = cell[u] >= 0 ? __hip_atomic_load(&plane[cell[u]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ~0ull;
         }
@@ -293,15 +293,7 @@ int frlw_eci_encode_batch(const frlw_events_t *ev, const int64_t *win_lo, const 
     for (int w = 0; w < n_win; ++w) { T.lo[w] = win_lo[w]; T.hi[w] = win_hi[w]; }
     if (!tab_ranges(T, ev, n_win)) return FRLW_ERR_ARG;
     EciLut L;
-    {   // generate_eventcountimage.py:32-34,41: n sequential f32 adds of 0.05f, > 1 -> 1, * 255 (as frlw_eci_encode builds it)
-        volatile float acc = 0.0f;
-        L.v[0] = 0.0f;
-        for (int n = 1; n <= 20; ++n) {
-            acc = acc + 0.05f;
-            float v = acc;
-            L.v[n] = (v > 1.0f ? 1.0f : v) * 255.0f;
-        }
-    }
+    eci_lut(L.v); // the table of frlw_eci_encode
     hipStream_t s = (hipStream_t)stream;
     WsHeader *hdr = (WsHeader *)workspace;
     uint32_t *cnt = (uint32_t *)((char *)workspace + kHeaderBytes);

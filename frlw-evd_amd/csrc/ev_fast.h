@@ -1,5 +1,5 @@
 // ev_fast.h -- the Event Volume consumers: the ticket sort of one wavefront (WavePass), kf_ev_sub and kf_ev_fadd.
-// Expects taf_decode.h (FastHeader, kMaxK) and taf_column.h.
+// Expects taf_decode.h (FastHeader), frlw_consts.h (kMaxK) and taf_column.h.
 #pragma once
 #include "taf_column.h"
 #include "taf_decode.h"

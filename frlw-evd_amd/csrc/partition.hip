@@ -18,8 +18,7 @@
 //               each tile's run (~chunk / n_tiles records) is completed in the L2 while it is hot.
 
 #include "frlw_common.h"
-
-#include <mutex>
+#include <type_traits>
 
 namespace frlw {
 
@@ -34,8 +33,6 @@ int hip_fail(hipError_t e, const char *what, int line)
 }
 
 namespace {
-
-// ---------------------------------------------------------------------------------------------
 template <int LAYOUT, int KIND, bool HAS_MAP>
 __global__ __launch_bounds__(kPartThreads) void k_hist(Decode P, int bpw, uint32_t *counts,
                                                         int32_t *errs, float *tlut_w)
@@ -174,14 +171,7 @@ __global__ __launch_bounds__(1024) void k_tilescan(uint32_t *slabtot, int slabs,
     if (tid == 0) fold_sticky_status(hdr, hdr->status); // every error flag was OR-ed in before the first barrier above
 }
 
-// ---------------------------------------------------------------------------------------------
-constexpr int kStageCap = 4096; // records staged in LDS per write-out window of the staged scatter
-// byte offset (16-aligned) of the staging area behind gs | wcnt | tag in the scatter workgroup's LDS
-__host__ __device__ inline size_t stage_off(int n_tiles)
-{
-    const size_t nt2 = (size_t)((n_tiles + 1) & ~1);
-    return ((size_t)n_tiles * 4 + (size_t)kPartWaves * nt2 * 2 + (size_t)kPartWaves * n_tiles + 15) & ~(size_t)15;
-}
+// (kStageCap, stage_off and the LDS sizes: enc_plan.h)
 template <int LAYOUT, int KIND, bool HAS_MAP, bool STAGED>
 __global__ __launch_bounds__(kPartThreads, 8) void k_scatter(Decode P, int bpw, const uint32_t *counts,
                                                            const uint32_t *slabtot,
@@ -209,7 +199,9 @@ __global__ __launch_bounds__(kPartThreads, 8) void k_scatter(Decode P, int bpw, 
     if (tid < P.n_tiles)
         gs_pre = base[tid] + slabtot[(wg / kSlabUnits) * (long long)P.n_tiles + tid] + counts[wg * (long long)P.n_tiles + tid];
     uint32_t where[kMaxBpw]; // tile << 16 | rank in (wave, tile); 0xffffffff = not encoded
+    static_assert(kWave * kMaxBpw <= 65535 && kMaxTiles <= 65536, "wcnt is uint16_t, the rank the low and the tile the high half of `where`");
     uint32_t cells[kMaxBpw / 2]; // strip-free cell of every event, two 16-bit values per register
+    static_assert((kTileH << 8) * 2 <= 65536, "a cell of the widest tile fits 16 bits");
     uint2 q[kMaxBpw];
     const long long left = P.n - wave_begin;
     const uint32_t nloc = left < (long long)kWave * bpw ? (uint32_t)(left < 0 ? 0 : left) : (uint32_t)(kWave * bpw);
@@ -230,8 +222,7 @@ __global__ __launch_bounds__(kPartThreads, 8) void k_scatter(Decode P, int bpw, 
         where[j] = 0xffffffffu;
         if (j < bpw) { // wave-uniform
             const uint32_t i = (uint32_t)(j * kWave + lane);
-            Pos o;
-            o.tile = -1; o.cell = 0; o.err = 0;
+            Pos o = {-1, 0u, 0};
             if (i < nloc) {
                 if (LAYOUT == FRLW_LAYOUT_DAT8) {
                     o = dat_pos<KIND, HAS_MAP>(P, q[j]);
@@ -381,111 +372,51 @@ __global__ __launch_bounds__(kPartThreads, 8) void k_scatter(Decode P, int bpw, 
     }
 }
 
+struct PartBufs { // the regions of the caller's workspace (Plan's offsets applied) that the four launches share
+    uint32_t *counts, *slabtot, *base; uint2 *records; WsHeader *hdr; int32_t *errs; float *tlut_w;
+};
+
 template <int LAYOUT, int KIND, bool HAS_MAP>
-void launch_partition_m(const Decode &d, const Plan &p, uint32_t *counts, uint32_t *slabtot,
-                      uint32_t *base, uint2 *records, WsHeader *hdr, int32_t *errs, float *tlut_w, hipStream_t s)
+void launch_partition(const Decode &d, const Plan &p, const PartBufs &b, hipStream_t s)
 {
-    const size_t lds_hist = (size_t)p.n_tiles * 4;
-    const int nt2 = (p.n_tiles + 1) & ~1;
-    const size_t lds_sc = (size_t)p.n_tiles * 4 + (size_t)kPartWaves * nt2 * 2 + (size_t)kPartWaves * p.n_tiles + 16;
-    const size_t lds_staged = stage_off(p.n_tiles) + (size_t)((p.n_tiles + 2 + 1) & ~1) * 4 + (size_t)kStageCap * 8 +
-                              (size_t)kStageCap * 2 + 16;
-    // staged write-out pays off for long streams with long chunks (10 M events: -11 us); on short ones the extra
-    // barriers cost more than the write traffic saves (GEN1-shaped 1 M events: 66 -> 74 us).
-    // frlw_tuning_t::staged_scatter forces it.
-    const bool staged = (p.staged >= 0 ? p.staged != 0 : (p.bpw >= 4 && d.n >= 3000000)) && lds_staged <= 150 * 1024;
-    hipLaunchKernelGGL((k_hist<LAYOUT, KIND, HAS_MAP>), dim3(p.units), dim3(kPartThreads), lds_hist, s, d, p.bpw, counts, errs, tlut_w);
-    hipLaunchKernelGGL(k_slabscan, dim3((p.n_tiles + kWave - 1) / kWave, p.slabs), dim3(kWave), 0, s, counts,
-                       p.units, p.n_tiles, slabtot);
-    hipLaunchKernelGGL(k_tilescan, dim3(1), dim3(1024), 0, s, slabtot, p.slabs, p.n_tiles, base, hdr, p.hot_thr, errs, p.units);
-    if (staged) {
-        if (lds_staged > 64 * 1024)
+    const ScatterLds l = scatter_lds(p, d.n);
+    hipLaunchKernelGGL((k_hist<LAYOUT, KIND, HAS_MAP>), dim3(p.units), dim3(kPartThreads), l.hist, s, d, p.bpw, b.counts, b.errs, b.tlut_w);
+    hipLaunchKernelGGL(k_slabscan, dim3((p.n_tiles + kWave - 1) / kWave, p.slabs), dim3(kWave), 0, s, b.counts, p.units, p.n_tiles, b.slabtot);
+    hipLaunchKernelGGL(k_tilescan, dim3(1), dim3(1024), 0, s, b.slabtot, p.slabs, p.n_tiles, b.base, b.hdr, p.hot_thr, b.errs, p.units);
+    if (l.staged) {
+        if (l.staged_bytes > 64 * 1024)
             (void)hipFuncSetAttribute((const void *)k_scatter<LAYOUT, KIND, HAS_MAP, true>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_staged);
-        hipLaunchKernelGGL((k_scatter<LAYOUT, KIND, HAS_MAP, true>), dim3(p.units), dim3(kPartThreads), lds_staged, s, d, p.bpw,
-                           counts, slabtot, base, records, hdr);
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.staged_bytes);
+        hipLaunchKernelGGL((k_scatter<LAYOUT, KIND, HAS_MAP, true>), dim3(p.units), dim3(kPartThreads), l.staged_bytes, s, d, p.bpw,
+                           b.counts, b.slabtot, b.base, b.records, b.hdr);
     } else {
-        hipLaunchKernelGGL((k_scatter<LAYOUT, KIND, HAS_MAP, false>), dim3(p.units), dim3(kPartThreads), lds_sc, s, d, p.bpw,
-                           counts, slabtot, base, records, hdr);
+        hipLaunchKernelGGL((k_scatter<LAYOUT, KIND, HAS_MAP, false>), dim3(p.units), dim3(kPartThreads), l.direct, s, d, p.bpw,
+                           b.counts, b.slabtot, b.base, b.records, b.hdr);
     }
 }
 
-template <int LAYOUT, int KIND>
-void launch_partition(const Decode &d, const Plan &p, uint32_t *counts, uint32_t *slabtot, uint32_t *base,
-                      uint2 *records, WsHeader *hdr, int32_t *errs, float *tlut_w, hipStream_t s)
-{
-    if (LAYOUT == FRLW_LAYOUT_DAT8 && d.xmap)
-        launch_partition_m<LAYOUT, KIND, true>(d, p, counts, slabtot, base, records, hdr, errs, tlut_w, s);
-    else
-        launch_partition_m<LAYOUT, KIND, false>(d, p, counts, slabtot, base, records, hdr, errs, tlut_w, s);
-}
-
+// event layout x encoder kind x coordinate maps -> the kernels' instances (the f64 layout has no maps: no such instance)
 template <int LAYOUT>
-void launch_partition_kind(int kind, const Decode &d, const Plan &p, uint32_t *counts, uint32_t *slabtot,
-                           uint32_t *base, uint2 *records, WsHeader *hdr, int32_t *errs, float *tlut_w, hipStream_t s)
+void dispatch_partition(int kind, const Decode &d, const Plan &p, const PartBufs &b, hipStream_t s)
 {
+    const auto go = [&](auto k) {
+        constexpr int KIND = decltype(k)::value;
+        if constexpr (LAYOUT == FRLW_LAYOUT_DAT8) {
+            if (d.xmap) return launch_partition<LAYOUT, KIND, true>(d, p, b, s);
+        }
+        launch_partition<LAYOUT, KIND, false>(d, p, b, s);
+    };
     switch (kind) {
-    case KIND_ECI: launch_partition<LAYOUT, KIND_ECI>(d, p, counts, slabtot, base, records, hdr, errs, tlut_w, s); break;
-    case KIND_EV: launch_partition<LAYOUT, KIND_EV>(d, p, counts, slabtot, base, records, hdr, errs, tlut_w, s); break;
-    case KIND_SAE: launch_partition<LAYOUT, KIND_SAE>(d, p, counts, slabtot, base, records, hdr, errs, tlut_w, s); break;
-    default: launch_partition<LAYOUT, KIND_TAF>(d, p, counts, slabtot, base, records, hdr, errs, tlut_w, s); break;
+    case KIND_ECI: go(std::integral_constant<int, KIND_ECI>{}); break;
+    case KIND_EV: go(std::integral_constant<int, KIND_EV>{}); break;
+    case KIND_SAE: go(std::integral_constant<int, KIND_SAE>{}); break;
+    default: go(std::integral_constant<int, KIND_TAF>{}); break;
     }
 }
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 } // namespace
 
-bool make_plan(long long n, int H, int W, const frlw_tuning_t *tuning, Plan &p)
-{
-    if (H <= 0 || W <= 0 || n < 0) return false;
-    const auto knob = [&](int32_t frlw_tuning_t::*f, int dflt) { return tuning_knob(tuning, f, dflt); };
-    p.twl = knob(&frlw_tuning_t::tile_width_log2, W > 512 ? 8 : 6);
-    if (p.twl < 6 || p.twl > 8) return false;
-    for (;; ++p.twl) { // tall frames (a batch of sequences stacked along y): widen the tiles to stay under kMaxTiles
-        const int tw = 1 << p.twl;
-        p.tiles_x = (W + tw - 1) / tw;
-        p.tiles_y = (H + kTileH - 1) / kTileH;
-        p.n_tiles = p.tiles_x * p.tiles_y;
-        if (p.n_tiles <= kMaxTiles || p.twl == 8) break;
-    }
-    if (p.n_tiles > kMaxTiles) return false;
-    // Workgroup chunk = kPartThreads * bpw events.  32 / kPartWaves partition workgroups fit on a CU, i.e.
-    // `slots` at a time on the chip: pick bpw so that the workgroup count lands just under a multiple of
-    // `slots` (whole rounds) with the longest chunk (= longest contiguous run per tile) that allows.
-    const long long slots = 256ll * (32 / kPartWaves);
-    int bpw = kMaxBpw;
-    for (int rounds = 1; rounds <= 64; ++rounds) {
-        const long long want = (n + slots * rounds * kPartThreads - 1) / (slots * rounds * kPartThreads);
-        if (want <= kMaxBpw) { bpw = (int)(want < 1 ? 1 : want); break; }
-    }
-    p.bpw = knob(&frlw_tuning_t::batches_per_wave, bpw);
-    if (p.bpw < 1 || p.bpw > kMaxBpw) return false;
-    p.chunk = (long long)kPartThreads * p.bpw;
-    p.units = (int)((n + p.chunk - 1) / p.chunk);
-    if (p.units < 1) p.units = 1;
-    p.slabs = (p.units + kSlabUnits - 1) / kSlabUnits;
-    size_t off = kHeaderBytes;
-    p.off_counts = off;  off = align_up(off + (size_t)p.units * p.n_tiles * 4, 256);
-    p.off_slabtot = off; off = align_up(off + (size_t)p.slabs * p.n_tiles * 4, 256);
-    p.off_base = off;    off = align_up(off + (size_t)(p.n_tiles + 1) * 4, 256);
-    p.off_errs = off;    off = align_up(off + (size_t)p.units * 4, 256);
-    p.off_tlut = off;    off = align_up(off + (size_t)(kMaxTlut + 1) * 4, 256);
-    p.off_records = off; off = align_up(off + (size_t)(n > 0 ? n : 1) * 8, 256);
-    p.bytes = off;
-    // more than two slices and more than 4x the mean: worth sharing (frlw_tuning_t::hot_tile_records: tests force it)
-    const long long slice2 = 2ll * kSliceMult * (4 << p.twl), mean4 = 4 * (n / p.n_tiles);
-    const long long thr = slice2 > mean4 ? slice2 : mean4;
-    p.hot_thr = (unsigned)knob(&frlw_tuning_t::hot_tile_records, thr > 0x7fffffffll ? 0x7fffffff : (int)thr);
-    p.staged = knob(&frlw_tuning_t::staged_scatter, -1);
-    p.quarter_below = knob(&frlw_tuning_t::quarter_below, 1024);
-    p.no_lut = knob(&frlw_tuning_t::no_value_table, 0);
-    return true;
-}
-
-int partition_events(const frlw_events_t *ev, int H, int W, int kind, long long t0, long long win,
-                     int n_windows, int time_filter, void *ws, size_t ws_bytes, hipStream_t s,
-                     Partitioned &out)
+int partition_events(const frlw_events_t *ev, int H, int W, int kind, long long t0, long long win, int n_windows, int time_filter,
+                     void *ws, size_t ws_bytes, hipStream_t s, Partitioned &out)
 {
     if (!ev || !ws || (ev->n > 0 && !ev->data)) return FRLW_ERR_ARG;
     if (ev->layout != FRLW_LAYOUT_XYTP_F64 && ev->layout != FRLW_LAYOUT_DAT8) return FRLW_ERR_ARG;
@@ -501,13 +432,8 @@ int partition_events(const frlw_events_t *ev, int H, int W, int kind, long long 
     if (!make_plan(ev->n, H, W, ev->tuning, p)) return FRLW_ERR_UNSUPPORTED;
     if (ws_bytes < p.bytes) return FRLW_ERR_WORKSPACE;
     char *w8 = (char *)ws;
-    WsHeader *hdr = (WsHeader *)w8;
-    uint32_t *counts = (uint32_t *)(w8 + p.off_counts);
-    uint32_t *slabtot = (uint32_t *)(w8 + p.off_slabtot);
-    uint32_t *base = (uint32_t *)(w8 + p.off_base);
-    int32_t *errs = (int32_t *)(w8 + p.off_errs);
-    uint2 *records = (uint2 *)(w8 + p.off_records);
-
+    PartBufs b = {(uint32_t *)(w8 + p.off_counts), (uint32_t *)(w8 + p.off_slabtot), (uint32_t *)(w8 + p.off_base),
+                  (uint2 *)(w8 + p.off_records), (WsHeader *)w8, (int32_t *)(w8 + p.off_errs), nullptr};
     Decode d;
     d.data = ev->data; d.n = ev->n; d.row_stride = ev->row_stride;
     d.xmap = ev->layout == FRLW_LAYOUT_DAT8 ? ev->xmap : nullptr;
@@ -517,87 +443,17 @@ int partition_events(const frlw_events_t *ev, int H, int W, int kind, long long 
     d.t0 = t0; d.win = win; d.n_windows = n_windows; d.time_filter = time_filter;
     const unsigned long long magic = (1ull << 32) / (unsigned long long)win;
     d.win_magic = magic > 0xffffffffull ? 0xffffffffu : (uint32_t)magic;
-    float *tlut_w = nullptr;
-    if (kind == KIND_TAF && ev->layout == FRLW_LAYOUT_DAT8 && win <= kMaxTlut && !p.no_lut) tlut_w = (float *)(w8 + p.off_tlut);
-    d.tlut = tlut_w;
+    if (kind == KIND_TAF && ev->layout == FRLW_LAYOUT_DAT8 && win <= kMaxTlut && !p.no_lut) b.tlut_w = (float *)(w8 + p.off_tlut);
+    d.tlut = b.tlut_w;
     const uint32_t *leaky = nullptr; // level thresholds of uint8(leaky_transform(.)) for the tile kernel's epilogue (generate_taf.py:69-76)
     if (kind == KIND_TAF && !(leaky = leaky_table(s))) return FRLW_ERR_HIP;
 
     (void)hipGetLastError(); // stale errors of other libraries in the process
-    if (ev->layout == FRLW_LAYOUT_DAT8)
-        launch_partition_kind<FRLW_LAYOUT_DAT8>(kind, d, p, counts, slabtot, base, records, hdr, errs, tlut_w, s);
-    else
-        launch_partition_kind<FRLW_LAYOUT_XYTP_F64>(kind, d, p, counts, slabtot, base, records, hdr, errs, tlut_w, s);
+    if (ev->layout == FRLW_LAYOUT_DAT8) dispatch_partition<FRLW_LAYOUT_DAT8>(kind, d, p, b, s);
+    else dispatch_partition<FRLW_LAYOUT_XYTP_F64>(kind, d, p, b, s);
     HIP_TRY(hipGetLastError());
-    out.records = records; out.base = base; out.hdr = hdr; out.plan = p; out.leaky_thr = leaky;
+    out.records = b.records; out.base = b.base; out.hdr = b.hdr; out.plan = p; out.leaky_thr = leaky;
     return FRLW_OK;
-}
-
-// ---- the uint8(leaky_transform(.)) threshold table: one per device, built on first use (see frlw_common.h) -----------
-namespace {
-__device__ uint32_t g_leaky_thr[kLeakyTableWords];
-__global__ __launch_bounds__(kLeakyLevels) void k_leaky_fill()
-{
-    __shared__ uint32_t thr[kLeakyLevels];
-    __shared__ uint8_t lut[kLeakyBuckets];
-    __shared__ int bad;
-    const int t = threadIdx.x;
-    thr[t] = t == 0 ? 0x7f800000u : leaky_threshold_bits(t); // generate_taf.py:69-76 as a 256-level step function
-    if (t == 0) bad = 0;
-    __syncthreads();
-    g_leaky_thr[t] = thr[t];
-    // the bucket table of leaky_u8_bucket_n: level(x) = the largest k with x <= thr[k] (thr is non-increasing in k)
-    auto level = [&](uint32_t xb) {
-        int lo = 0, hi = kLeakyLevels; // thr[lo] >= xb always (thr[0] = +inf); first k with thr[k] < xb is in (lo, hi]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (xb <= thr[mid]) lo = mid; else hi = mid;
-        }
-        return lo;
-    };
-    for (int b = t; b < kLeakyBuckets; b += kLeakyLevels) {
-        const uint32_t lo_x = b == 0 ? 0u : (uint32_t)(b + kLeakyBucket0) << kLeakyBucketShift;
-        const uint32_t hi_x = b == kLeakyBuckets - 1 ? 0x7f800000u : (((uint32_t)(b + kLeakyBucket0 + 1)) << kLeakyBucketShift) - 1u;
-        const int k_hi = level(hi_x), k_lo = level(lo_x);
-        lut[b] = (uint8_t)k_hi;
-        if (k_lo - k_hi > 1 || k_hi > kLeakyLevels - 2) bad = 1; // more than one threshold inside the bucket: the table is not used
-    }
-    __syncthreads();
-    for (int w = t; w < kLeakyBuckets / 4; w += kLeakyLevels)
-        g_leaky_thr[kLeakyLutWord + w] = (uint32_t)lut[4 * w] | ((uint32_t)lut[4 * w + 1] << 8) | ((uint32_t)lut[4 * w + 2] << 16) | ((uint32_t)lut[4 * w + 3] << 24);
-    if (t == 0) g_leaky_thr[kLeakyOkWord] = bad ? 0u : 1u;
-}
-struct LeakyDev { int state = 0; hipEvent_t ev = nullptr; const uint32_t *ptr = nullptr; }; // 0 never filled, 1 fill queued, 2 done
-std::mutex g_leaky_mu;
-LeakyDev g_leaky_dev[64];
-} // namespace
-
-const uint32_t *leaky_table(hipStream_t s)
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    std::lock_guard<std::mutex> lock(g_leaky_mu);
-    LeakyDev &d = g_leaky_dev[dev];
-    if (!d.ptr) {
-        void *p = nullptr;
-        if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_leaky_thr)) != hipSuccess) return nullptr;
-        d.ptr = (const uint32_t *)p;
-    }
-    if (d.state == 2) return d.ptr;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(s, &cap);
-    if (cap != hipStreamCaptureStatusNone) { // the fill becomes a node of that graph (idempotent); nothing is remembered
-        hipLaunchKernelGGL(k_leaky_fill, dim3(1), dim3(kLeakyLevels), 0, s);
-        return d.ptr;
-    }
-    if (d.state == 0) { // in front of the caller's kernels on its own stream
-        hipLaunchKernelGGL(k_leaky_fill, dim3(1), dim3(kLeakyLevels), 0, s);
-        if (hipEventCreateWithFlags(&d.ev, hipEventDisableTiming) == hipSuccess && hipEventRecord(d.ev, s) == hipSuccess) d.state = 1;
-        return d.ptr; // (no event: the next call fills again)
-    }
-    if (hipEventQuery(d.ev) == hipSuccess) d.state = 2;
-    else if (hipStreamWaitEvent(s, d.ev, 0) != hipSuccess) return nullptr;
-    return d.ptr;
 }
 
 } // namespace frlw

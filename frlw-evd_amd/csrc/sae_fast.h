@@ -10,7 +10,7 @@ namespace {
 // order, max with the memory, exp(lambda (t_img - now)) * 255.  The general path takes five launches (41 us for 1 M events at
 // 304x240).  Here: kf_scatter_cm<.., SAE> writes records {position in the sequence << 12 | cell} chunk-major, and one workgroup
 // per sub-tile takes the maximum record per cell with LDS atomics -- straight from the runs, no list, no order needed -- reads
-// the time of that one event from the DAT array and writes memory and outputs with the arithmetic of k_sae_tile (encoders.hip).
+// the time of that one event from the DAT array and writes memory and outputs with the arithmetic of k_sae_tile (enc_sae.h).
 struct SaeFastP {
     int H, W, twl, thl, tiles_x, T, n_lamda;
     float lam[FRLW_MAX_LAMDAS > 21 ? FRLW_MAX_LAMDAS : 21]; // (ECI: the count -> value table)

@@ -1,4 +1,4 @@
-// taf_decode.h -- a DAT record -> (bin, 4-byte record word, window): FastGeom, the workspace header, the decode functions, kMaxK.
+// taf_decode.h -- a DAT record -> (bin, 4-byte record word, window): FastGeom, the workspace header, the decode functions.
 // Expects frlw_common.h (ST_*, kSelftestOffset) and taf_plan.h (constants, SeqTab).
 #pragma once
 #include "frlw_common.h"
@@ -6,7 +6,6 @@
 
 namespace {
 using namespace frlw;
-constexpr int kMaxK = 8; // TAF FIFO depth / Event Volume bins a cell keeps in registers (FRLW_MAX_BINS)
 struct FastGeom {
     const uint2 *data;
     const uint16_t *xmap, *ymap;

@@ -427,7 +427,7 @@ int taf_batch_run(int phases, const frlw_events_t *ev, const int64_t *seq_offset
     q.H = H; q.W = W; q.twl = p.twl; q.thl = p.thl; q.tiles_x = p.tiles_x; q.K = K; q.n_windows = n_windows;
     q.wb = wb; q.flip = (flags & FRLW_TAF_U8_FLIP_K) ? 1 : 0; q.win = (uint32_t)window_us; q.rcp = G.rcp;
     q.tlut = (const float *)(w8 + p.off_tlut);
-    if (!(q.leaky_thr = leaky_table(st))) return FRLW_ERR_HIP; // device-resident constant, built once per device (partition.hip)
+    if (!(q.leaky_thr = leaky_table(st))) return FRLW_ERR_HIP; // device-resident constant, built once per device (leaky.hip)
     q.state = state; q.view_f32 = view_f32; q.out_u8 = out_u8;
     if (cm && !p.direct && tuning_knob(ev->tuning, &frlw_tuning_t::walk_window_table, 1) != 0) { // kf_split_whole<true> leaves the walk its window starts
         q.wst = (uint32_t *)(w8 + p.off_wst);

@@ -1,25 +1,10 @@
 // taf_walk.h -- kf_taf_walk: one workgroup per sub-tile list, a window per wavefront, then the FIFO steps.
-// Expects taf_split.h (TileP), taf_decode.h (kMaxK) and taf_column.h; the leaky table (kLeakyTableWords, frlw_common.h).
+// Expects taf_split.h (TileP), taf_fifo.h (fifo_step, fifo_mean, kMaxK) and taf_column.h; the leaky table (kLeakyTableWords, leaky.h).
 #pragma once
+#include "taf_fifo.h"
 #include "taf_split.h"
 
 namespace {
-// One FIFO step of one cell, generate_taf.py:27,35-49.  Cell without events: every slot - 1; otherwise shift down
-// (slot k + 1, - 1) and the mean enters at K - 1.  `has` false (window empty in the whole sequence, :40-41): unchanged.
-__device__ __forceinline__ float fifo_mean(uint32_t n, float sum) { return sum / ((float)n + 1e-8f); } // generate_taf.py:27
-
-__device__ __forceinline__ void fifo_step(float (&st)[kMaxK], int K, bool has, uint32_t n, float mean)
-{
-    const bool hit = n != 0u;
-#pragma unroll
-    for (int k = 0; k < kMaxK; ++k) {
-        const float nxt = k + 1 < kMaxK ? st[k + 1] : 0.0f;
-        const float v = (hit ? nxt : st[k]) - 1.0f;
-        const float nv = (hit && k == K - 1) ? mean : v;
-        st[k] = has ? nv : st[k];
-    }
-}
-
 // The same step for K = 8 with TWO lanes per cell: the even lane holds slots 0..3, the odd lane slots 4..7 of the row
 // (the whole workgroup works in phase 2, and a lane moves 16 bytes of the row).  Slot 3 takes over slot 4 from the
 // partner lane through a DPP row shift; the float operations per slot are those of fifo_step.

@@ -3,6 +3,9 @@
 
     hipcc <_build.HIPCC_FLAGS without -shared> -I include -I frlw-evd_amd/csrc --cuda-device-only -S csrc/taf_fast.hip -o new.s
     python tools/asm_equal.py parent.s new.s
+    python tools/asm_equal.py parent.encoders.s,parent.partition.s new.encoders.s,new.partition.s,new.leaky.s
+
+Either side may be several listings joined by commas (code that moved to another translation unit): they are read as one.
 
 Lines that carry only file names, line numbers or the identity of the compilation (.file, .loc, .ident, the __hip_cuid_<hash of
 the source> symbol) are dropped first.  Local labels carry the function's ordinal in the listing (.LBB12_3, .Lfunc_end12), which moves
@@ -16,9 +19,12 @@ import re
 import sys
 
 
-def load(path):
-    with open(path) as f:
-        return [l.rstrip() for l in f if not re.match(r"\s*\.(file|loc|ident)\b", l) and "__hip_cuid_" not in l]
+def load(paths):
+    out = []
+    for path in paths.split(","):
+        with open(path) as f:
+            out += [l.rstrip() for l in f if not re.match(r"\s*\.(file|loc|ident)\b", l) and "__hip_cuid_" not in l]
+    return out
 
 
 def functions(lines):
@@ -30,13 +36,14 @@ def functions(lines):
             out[cur] = []
         if cur:
             out[cur].append(l)
-        if l.startswith(".Lfunc_end"):
+        if l.startswith(".Lfunc_end") or (cur and l.startswith("\t.size\t" + cur + ",")):  # (.size: where a variable ends)
             cur = None
     return out
 
 
 def unnumbered(body):
-    return body and [re.sub(r"(\.LBB|\bBB|\.Lfunc_end)\d+", r"\1", l) for l in body]
+    # (the comment behind a label is padded to a column: with the ordinal out, so is the padding)
+    return body and [re.sub(r":\s+;", ": ;", re.sub(r"(\.LBB|\bBB|\.Lfunc_end)\d+", r"\1", l)) for l in body]
 
 
 def main():
