@@ -122,6 +122,13 @@ SYMBOLS = {
     "frlw_sae_encode_batch": (_I, [_EV, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _I, _I, _I, C.POINTER(C.c_double), _I, _P, _P,
                                   _I64, _P, _P, _P, _SZ, _P]),
     "frlw_encoder_batch_counts": (_I, [C.POINTER(C.c_uint64)]),
+    "frlw_sae_chain_workspace_bytes": (_SZ, [_I64, _I, _I, _I]),
+    "frlw_sae_encode_chain": (_I, [_EV, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                  C.POINTER(C.c_uint8), _I, _I, _I, C.POINTER(C.c_double), _I, _P, _P, _P, _P, _P, _SZ, _P]),
+    "frlw_ev_ranges_workspace_bytes": (_SZ, [_I64, _I, _I, _I, _I64]),
+    "frlw_ev_encode_ranges": (_I, [_EV, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _I, _I, _I, _I, _I64, _P, _P,
+                                  _P, _SZ, _P]),
+    "frlw_encoder_chain_counts": (_I, [C.POINTER(C.c_uint64)]),
     "frlw_leaky_transform": (_I, [_P, _I64, _P, _P, _P]),
     "frlw_resize_nearest_f32": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "frlw_resize_nearest_u8": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),

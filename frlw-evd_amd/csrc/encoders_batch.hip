@@ -17,6 +17,12 @@
 //
 // Three launches per call, no host synchronisation, nothing but the caller's workspace: capturable.  Windows of the count image may
 // overlap or nest (the three nested windows per label of the offline command): each is a record range of its own.
+//
+// frlw_sae_encode_chain: the labels of ONE file are a chain (the memory label l leaves is the input of label l + 1), but only the
+// last step of the surface is sequential -- the last writer of a cell within a step does not depend on the memory.  So the steps'
+// key planes are filled by the same kb_sae_last launch (a step is a record range with its own now and window), and
+//   kb_sae_chain_out   runs the scan over the steps per cell, the memory in a register, and stores the volumes of the emitting steps
+// replaces kb_sae_out: kb_zero, kb_sae_last, kb_sae_chain_out for up to 64 labels.
 
 #include "frlw_common.h"
 
@@ -217,6 +223,55 @@ __global__ __launch_bounds__(256) void kb_sae_out(const unsigned long long *last
     }
 }
 
+// ---- Surface of Active Events, chained steps -----------------------------------------------------
+// The steps of one chain, by value like BatchTab: float(now) of step s and where its volume goes (-1: the step only advances the memory)
+struct ChainTab {
+    float nowf[kMaxSeq];
+    int slot[kMaxSeq];
+    int n;
+};
+
+constexpr int kChainU = 8; // steps whose keys are in flight before the first is used
+
+// One thread per cell of the ONE (2, H, W) memory plane, the running memory in a register: the scan over the steps that
+// n calls of kb_sae_out would make through mem_in / mem_out.  The keys do not depend on the memory, so kChainU steps' loads are
+// issued together (planes are step-major: every load and store is coalesced across the workgroup).
+__global__ __launch_bounds__(256) void kb_sae_chain_out(const unsigned long long *last, long long cells, ChainTab T, SaeOutP q)
+{
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x; c < cells; c += stride) {
+        bool has = q.mem_in != nullptr;
+        float m = has ? q.mem_in[c] : 0.0f;
+        for (int s0 = 0; s0 < T.n; s0 += kChainU) {
+            unsigned long long key[kChainU];
+#pragma unroll
+            for (int u = 0; u < kChainU; ++u) key[u] = s0 + u < T.n ? last[(long long)(s0 + u) * cells + c] : 0ull;
+#pragma unroll
+            for (int u = 0; u < kChainU; ++u) {
+                const int s = s0 + u;
+                if (s < T.n) {
+                    const float nowf = T.nowf[s];
+                    float tv = key[u] ? __uint_as_float((uint32_t)key[u]) : (0.0f + nowf) - 5000000.0f; // kb_sae_out's value
+                    if (has && !(tv > m)) tv = m; // torch.where(t_img > memory, t_img, memory)
+                    m = tv;
+                    has = true;
+                    const int slot = T.slot[s];
+                    if (slot >= 0) {
+                        const float dt = m - nowf;
+                        for (int l = 0; l < q.n_lamda; ++l) {
+                            const float v = expf(q.lam[l] * dt) * 255.0f;
+                            const long long oi = ((long long)slot * q.n_lamda + l) * cells + c;
+                            if (q.out_f32) q.out_f32[oi] = v;
+                            if (q.out_u8) q.out_u8[oi] = f32_to_u8(v);
+                        }
+                    }
+                }
+            }
+        }
+        q.mem_out[c] = m;
+    }
+}
+
 // ---- host --------------------------------------------------------------------------------------
 std::atomic<unsigned long long> g_batch_counts[2]; // calls served: [0] Event Count Image, [1] Surface of Active Events
 
@@ -259,12 +314,23 @@ BatchDecode decode_of(const frlw_events_t *ev, int H, int W)
 
 } // namespace
 
+namespace frlw {
+std::atomic<unsigned long long> g_chain_counts[2]; // calls served: [0] frlw_sae_encode_chain, [1] frlw_ev_encode_ranges (taf_fast.hip)
+}
+
 extern "C" {
 
 int frlw_encoder_batch_counts(uint64_t counts[2])
 {
     if (!counts) return FRLW_ERR_ARG;
     for (int i = 0; i < 2; ++i) counts[i] = (uint64_t)g_batch_counts[i].load(std::memory_order_relaxed);
+    return FRLW_OK;
+}
+
+int frlw_encoder_chain_counts(uint64_t counts[2])
+{
+    if (!counts) return FRLW_ERR_ARG;
+    for (int i = 0; i < 2; ++i) counts[i] = (uint64_t)g_chain_counts[i].load(std::memory_order_relaxed);
     return FRLW_OK;
 }
 
@@ -353,6 +419,60 @@ int frlw_sae_encode_batch(const frlw_events_t *ev, const int64_t *seq_offsets, c
     hipLaunchKernelGGL(kb_sae_out, dim3(gx, n_seq), dim3(256), 0, s, (const unsigned long long *)last, cells, T, q);
     HIP_TRY(hipGetLastError());
     g_batch_counts[1].fetch_add(1ull, std::memory_order_relaxed);
+    return FRLW_OK;
+}
+
+size_t frlw_sae_chain_workspace_bytes(int64_t n_records, int n_steps, int H, int W)
+{
+    return n_records < 0 ? 0 : batch_bytes(n_steps, H, W, sizeof(unsigned long long)); // one key plane per step
+}
+
+int frlw_sae_encode_chain(const frlw_events_t *ev, const int64_t *step_lo, const int64_t *step_hi, const int64_t *now,
+                          const int64_t *window_us, const uint8_t *emit, int n_steps, int H, int W, const double *lamdas, int n_lamda,
+                          const float *mem_in, float *mem_out, float *out_f32, uint8_t *out_u8, void *workspace,
+                          size_t workspace_bytes, frlw_stream_t stream)
+{
+    if (!step_lo || !step_hi || !now || !window_us || !emit || !mem_out || !workspace || n_steps < 1 || n_steps > kMaxSeq) return FRLW_ERR_ARG;
+    if (n_lamda < 0 || n_lamda > FRLW_MAX_LAMDAS || (n_lamda > 0 && !lamdas)) return FRLW_ERR_ARG;
+    {
+        const int rc = events_check(ev);
+        if (rc != FRLW_OK) return rc;
+    }
+    const size_t need = batch_bytes(n_steps, H, W, sizeof(unsigned long long));
+    if (need == 0) return FRLW_ERR_ARG;
+    if (workspace_bytes < need) return FRLW_ERR_WORKSPACE;
+    BatchTab T = {};
+    ChainTab Ch = {};
+    int n_emit = 0;
+    for (int s = 0; s < n_steps; ++s) {
+        T.lo[s] = step_lo[s]; T.hi[s] = step_hi[s];
+        // kb_sae_last keeps an event with t > t0 (t is a 32-bit unsigned): the smallest t0 keeps every event, which is what
+        // window_us <= 0 asks for -- the per-step filter without a second form of the kernel
+        T.t0[s] = window_us[s] > 0 ? now[s] - window_us[s] : INT64_MIN;
+        T.nowf[s] = Ch.nowf[s] = (float)now[s];
+        Ch.slot[s] = emit[s] ? n_emit++ : -1;
+    }
+    Ch.n = n_steps;
+    if (n_emit > 0 && !out_f32 && !out_u8) return FRLW_ERR_ARG;
+    if (!tab_ranges(T, ev, n_steps)) return FRLW_ERR_ARG;
+    SaeOutP q;
+    q.n_lamda = n_lamda;
+    for (int l = 0; l < FRLW_MAX_LAMDAS; ++l) q.lam[l] = l < n_lamda ? (float)lamdas[l] : 0.0f;
+    q.mem_in = mem_in; q.mem_out = mem_out; q.out_f32 = out_f32; q.out_u8 = out_u8;
+    hipStream_t st = (hipStream_t)stream;
+    WsHeader *hdr = (WsHeader *)workspace;
+    unsigned long long *last = (unsigned long long *)((char *)workspace + kHeaderBytes);
+    const long long cells = 2ll * H * W;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(kb_zero, dim3(grid_for(n_steps * cells / 2, 256)), dim3(256), 0, st, (uint4 *)last, n_steps * cells / 2, hdr);
+    const BatchDecode D = decode_of(ev, H, W);
+    if (T.blk[n_steps] > 0u) {
+        if (ev->xmap) hipLaunchKernelGGL(kb_sae_last<true>, dim3(T.blk[n_steps]), dim3(kBT), 0, st, D, T, 1, last, hdr);
+        else hipLaunchKernelGGL(kb_sae_last<false>, dim3(T.blk[n_steps]), dim3(kBT), 0, st, D, T, 1, last, hdr);
+    }
+    hipLaunchKernelGGL(kb_sae_chain_out, dim3(grid_for(cells, 256)), dim3(256), 0, st, (const unsigned long long *)last, cells, Ch, q);
+    HIP_TRY(hipGetLastError());
+    g_chain_counts[0].fetch_add(1ull, std::memory_order_relaxed);
     return FRLW_OK;
 }
 

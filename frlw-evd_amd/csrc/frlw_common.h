@@ -110,6 +110,8 @@ int sae_fast_try(const frlw_events_t *ev, int H, int W, const float *lam, int n_
 // frlw_encoder_path_counts: [0] SAE two-launch, [1] SAE general, [2] ECI two-launch, [3] ECI single-launch scan / general.
 size_t sae_fast_workspace_bytes(long long n, int H, int W);
 extern std::atomic<unsigned long long> g_path_counts[4];
+// behind frlw_encoder_chain_counts (encoders_batch.hip): [0] frlw_sae_encode_chain, [1] frlw_ev_encode_ranges
+extern std::atomic<unsigned long long> g_chain_counts[2];
 
 // hist -> scans -> stable scatter: tile-major 8-byte records {window << (twl + 4) | cell, f32 bits}.
 int partition_events(const frlw_events_t *ev, int H, int W, int kind, long long t0, long long win, int n_windows, int time_filter,

@@ -26,10 +26,12 @@
 //
 // The files (each says in its first lines what it holds and expects): taf_plan.h the host planner (no HIP: tested on the CPU),
 // taf_decode.h records, taf_partition.h both partitions, taf_column.h a bin's column of the chunk-major directory, taf_split.h the
-// second level, taf_walk.h kf_taf_walk, ev_fast.h / sae_fast.h the Event Volume and SAE / Event Count Image consumers.  Here: the
+// second level, taf_walk.h kf_taf_walk, ev_fast.h / sae_fast.h the Event Volume and SAE / Event Count Image consumers, ev_ranges.h the
+// gather in front of the Event Volume batch for windows given as record ranges (frlw_ev_encode_ranges).  Here: the
 // lane-order self-test, the launch helpers and the C entry points.
 
 #include "ev_fast.h"
+#include "ev_ranges.h"
 #include "sae_fast.h"
 #include "taf_walk.h"
 
@@ -481,9 +483,13 @@ size_t frlw_ev_batch_workspace_bytes(int64_t n_events, int n_seq, int H, int W, 
     return frlw_taf_batch_workspace_bytes(n_events, n_seq, H, W, window_us); // same partition, same tables
 }
 
-int frlw_ev_encode_batch(const frlw_events_t *ev, const int64_t *seq_offsets, const int64_t *t_end, int n_seq, int H, int W,
-                         int bins, int64_t window_us, float *out_f32, uint8_t *out_u8, void *workspace,
-                         size_t workspace_bytes, frlw_stream_t stream)
+} // extern "C"
+
+namespace {
+// The body of frlw_ev_encode_batch; frlw_ev_encode_ranges runs it on its copy of the windows' records.
+int ev_batch_run(const frlw_events_t *ev, const int64_t *seq_offsets, const int64_t *t_end, int n_seq, int H, int W,
+                 int bins, int64_t window_us, float *out_f32, uint8_t *out_u8, void *workspace,
+                 size_t workspace_bytes, frlw_stream_t stream, const RangeTab *gather = nullptr, const uint2 *gather_src = nullptr)
 {
     if (!out_f32 && !out_u8) return FRLW_ERR_ARG;
     if (bins < 1 || bins > FRLW_MAX_BINS || window_us < 1) return FRLW_ERR_ARG;
@@ -517,6 +523,8 @@ int frlw_ev_encode_batch(const frlw_events_t *ev, const int64_t *seq_offsets, co
         const int ok = lds_order_ok(w8, st); // cached per device after the first call
         if (ok != FRLW_OK) return ok;
     }
+    if (gather && gather->blk[gather->n] > 0u) // every check has passed: the copy the partition is about to read
+        hipLaunchKernelGGL(kf_gather_ranges, dim3(gather->blk[gather->n]), dim3(kGT), 0, st, gather_src, *gather, (uint2 *)ev->data);
     launch_partition<true>(G, S, p, cm, w8, st);
     TileP q = {}; // second level: kf_split_whole + kf_ev_sub (one wavefront per sub-tile list)
     launch_second_level(q, p, S, cm, w8, st);
@@ -545,6 +553,70 @@ int frlw_ev_encode_batch(const frlw_events_t *ev, const int64_t *seq_offsets, co
     } else if (bins <= 5) hipLaunchKernelGGL((kf_ev_sub<5, false>), dim3(sub_grid), dim3(4 * kWave), 0, st, e, cmq, S);
     else hipLaunchKernelGGL((kf_ev_sub<kMaxK, false>), dim3(sub_grid), dim3(4 * kWave), 0, st, e, cmq, S);
     HIP_TRY(hipGetLastError());
+    return FRLW_OK;
+}
+} // namespace
+
+extern "C" {
+
+int frlw_ev_encode_batch(const frlw_events_t *ev, const int64_t *seq_offsets, const int64_t *t_end, int n_seq, int H, int W,
+                         int bins, int64_t window_us, float *out_f32, uint8_t *out_u8, void *workspace,
+                         size_t workspace_bytes, frlw_stream_t stream)
+{
+    return ev_batch_run(ev, seq_offsets, t_end, n_seq, H, W, bins, window_us, out_f32, out_u8, workspace, workspace_bytes, stream);
+}
+
+// The batch call's workspace comes FIRST (its header is the workspace header: status, sticky status and the self-test result
+// stay where frlw_workspace_init / frlw_encoder_deferred_status expect them), the copy of the windows' records behind it.
+static size_t ranges_copy_offset(int64_t n_gathered, int n_win, int H, int W, int64_t window_us)
+{
+    const size_t inner = frlw_ev_batch_workspace_bytes(n_gathered, n_win, H, W, window_us);
+    return inner ? frlw::align_up(inner, 256) : 0;
+}
+
+size_t frlw_ev_ranges_workspace_bytes(int64_t n_gathered, int n_win, int H, int W, int64_t window_us)
+{
+    if (n_gathered < 0 || n_win < 1 || n_win > kMaxSeq) return 0;
+    const size_t off = ranges_copy_offset(n_gathered, n_win, H, W, window_us);
+    return off ? off + frlw::align_up((size_t)n_gathered * 8, 16) : 0;
+}
+
+int frlw_ev_encode_ranges(const frlw_events_t *ev, const int64_t *win_lo, const int64_t *win_hi, const int64_t *t_end, int n_win,
+                          int H, int W, int bins, int64_t window_us, float *out_f32, uint8_t *out_u8, void *workspace,
+                          size_t workspace_bytes, frlw_stream_t stream)
+{
+    if (!out_f32 && !out_u8) return FRLW_ERR_ARG;
+    if (bins < 1 || bins > FRLW_MAX_BINS || window_us < 1) return FRLW_ERR_ARG;
+    if (!ev || !win_lo || !win_hi || !t_end || !workspace || n_win < 1 || n_win > kMaxSeq) return FRLW_ERR_ARG;
+    if (ev->layout != FRLW_LAYOUT_DAT8) return FRLW_ERR_UNSUPPORTED;
+    RangeTab T = {};
+    int64_t offs[kMaxSeq + 1];
+    unsigned long long blocks = 0;
+    offs[0] = 0;
+    for (int w = 0; w < n_win; ++w) {
+        if (win_lo[w] < 0 || win_hi[w] < win_lo[w] || win_hi[w] > ev->n) return FRLW_ERR_ARG;
+        T.lo[w] = win_lo[w];
+        T.dst[w] = offs[w];
+        T.blk[w] = (uint32_t)blocks;
+        offs[w + 1] = offs[w] + (win_hi[w] - win_lo[w]);
+        if (offs[w + 1] >= (1ll << 31)) return FRLW_ERR_UNSUPPORTED; // (the partition's own limit on a call's records)
+        blocks += (unsigned long long)((win_hi[w] - win_lo[w] + kGSlice - 1) / kGSlice); // (< 2^31 / kGSlice + 64: fits 32 bits)
+    }
+    for (int w = n_win; w <= kMaxSeq; ++w) { T.dst[w] = offs[n_win]; T.blk[w] = (uint32_t)blocks; }
+    T.n = n_win;
+    const int64_t n_gathered = offs[n_win];
+    if (n_gathered > 0 && !ev->data) return FRLW_ERR_ARG;
+    const size_t copy_off = ranges_copy_offset(n_gathered, n_win, H, W, window_us);
+    if (copy_off == 0) return (H <= 0 || W <= 0) ? FRLW_ERR_ARG : FRLW_ERR_UNSUPPORTED;
+    if (workspace_bytes < copy_off + frlw::align_up((size_t)n_gathered * 8, 16)) return FRLW_ERR_WORKSPACE;
+    uint2 *copy = (uint2 *)((char *)workspace + copy_off);
+    frlw_events_t local = *ev; // maps and tuning are the caller's, the records are the copy
+    local.data = copy;
+    local.n = n_gathered;
+    const int rc = ev_batch_run(&local, offs, t_end, n_win, H, W, bins, window_us, out_f32, out_u8, workspace, copy_off, stream, &T,
+                                (const uint2 *)ev->data);
+    if (rc != FRLW_OK) return rc;
+    g_chain_counts[1].fetch_add(1ull, std::memory_order_relaxed);
     return FRLW_OK;
 }
 

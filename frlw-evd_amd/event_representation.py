@@ -538,6 +538,61 @@ def encode_ev_batch(dat, seq_offsets, shape, t_end, window_us, volume_bins=5, wa
     return out, u8
 
 
+def ev_ranges_max_windows(shape, window_us):
+    """The most windows one ``encode_ev_ranges`` call takes at this shape (host arithmetic: the partition keeps at most 8192
+    (window, tile) pairs, so 512 x 640 frames take 51 windows, GEN1 frames all 64); 0 = the shape / window is outside the path."""
+    H, W = int(shape[0]), int(shape[1])
+    query = _lib.load().frlw_ev_ranges_workspace_bytes
+    for b in range(_lib.MAX_SEQUENCES, 0, -1):
+        if query(0, b, H, W, int(window_us)):
+            return b
+    return 0
+
+
+def encode_ev_ranges(dat, ranges, shape, t_end, window_us, volume_bins=5, want_f32=True, want_u8=False, xmap=None, ymap=None,
+                     check=True):
+    """generate_eventvolume.py:139-157 for label windows given as record ranges, in one launch sequence
+    (``frlw_ev_encode_ranges``, csrc/taf_fast.hip): window ``b`` is the records ``dat[lo:hi]`` of ``ranges[b] = (lo, hi)`` and ends
+    at ``t_end[b]`` (an int applies to all); windows may overlap, nest or be empty -- the label slices of one file.  One launch
+    copies the ranges one behind the other into the workspace, then ``encode_ev_batch``'s kernels run on the copy.  Returns
+    ``(f32 (B, 2 * bins, H, W) or None, u8 or None)`` -- bit for bit what ``encode_ev_dat`` gives per range.  Raises what
+    ``encode_ev_batch`` raises (``ValueError`` outside 1..64 windows, for a range that runs backwards or leaves ``dat`` and, with
+    ``check``, for an event behind its ``t_end``: nothing is written; ``NotImplementedError``: shape / window outside the path, the
+    fast path switched off).  A workspace slot of its own."""
+    H, W = int(shape[0]), int(shape[1])
+    rng = [(int(lo), int(hi)) for lo, hi in ranges]
+    B = len(rng)
+    if B < 1 or B > _lib.MAX_SEQUENCES:
+        raise ValueError(f"1..{_lib.MAX_SEQUENCES} windows per call")
+    if not want_f32 and not want_u8:
+        raise ValueError("nothing to return: want_f32 or want_u8")
+    te = [int(t_end)] * B if not hasattr(t_end, "__len__") else [int(t) for t in t_end]
+    if len(te) != B:
+        raise ValueError("one `t_end` per window")
+    n = dat.numel() * dat.element_size() // 8
+    for lo, hi in rng:
+        if lo < 0 or hi < lo or hi > n:
+            raise ValueError(f"record range ({lo}, {hi}) outside 0 <= lo <= hi <= {n}")
+    if not FAST_PATH_ENABLED:
+        raise NotImplementedError("the fast path is switched off for this job (dist.agree_fast_path: a rank failed the self-test)")
+    d, desc = _events_dat(dat, xmap, ymap)
+    need = _lib.load().frlw_ev_ranges_workspace_bytes(sum(hi - lo for lo, hi in rng), B, H, W, int(window_us))
+    if need == 0:
+        raise NotImplementedError("shape / window outside the ranged Event Volume path")
+    ws = _slot_workspace(need, d.device, "ev_ranges")
+    out = torch.empty((B, 2 * volume_bins, H, W), dtype=torch.float32, device=d.device) if want_f32 else None
+    u8 = torch.empty((B, 2 * volume_bins, H, W), dtype=torch.uint8, device=d.device) if want_u8 else None
+    rc = _lib.load().frlw_ev_encode_ranges(C.byref(desc), (C.c_int64 * B)(*[r[0] for r in rng]), (C.c_int64 * B)(*[r[1] for r in rng]),
+                                           (C.c_int64 * B)(*te), B, H, W, int(volume_bins), int(window_us), _ptr(out), _ptr(u8),
+                                           _ptr(ws), ws.numel(), _stream())
+    if rc == _lib.FRLW_ERR_UNSUPPORTED:
+        raise NotImplementedError("window / shape outside the ranged Event Volume path")
+    _lib.check(rc, "encode_ev_ranges")
+    if check:
+        _finish(ws, "encode_ev_ranges")
+    return out, u8
+
+
 def encode_eci_dat(dat, shape, want_f32=True, want_u8=False, xmap=None, ymap=None, check=True):
     """generate_eventcountimage.py:155-180 on device (the caller has cut the last ``events_window`` records)."""
     H, W = int(shape[0]), int(shape[1])
@@ -662,4 +717,54 @@ def encode_sae_batch(dat, seq_offsets, shape, lamdas, memory, now, window_us, wa
     _lib.check(rc, "encode_sae_batch")
     if check:
         _finish(ws, "encode_sae_batch")
+    return out, u8, mem_out
+
+
+def encode_sae_chain(dat, steps, shape, lamdas, memory, want_f32=True, want_u8=False, xmap=None, ymap=None, check=True):
+    """generate_surfaceofactiveevents.py:147-200 for a CHAIN of steps on one memory plane, in one launch sequence
+    (``frlw_sae_encode_chain``): ``steps[s] = (lo, hi, now, window_us, emit)`` encodes the records ``dat[lo:hi]`` on the memory step
+    ``s - 1`` left (step 0: ``memory`` ``(2, H, W)``, or ``None`` = no memory yet); ranges may overlap, nest, repeat or be empty,
+    ``window_us <= 0`` keeps every event.  Only the steps with ``emit`` write a volume.  Returns ``(f32 (E, 2 * len(lamdas), H, W)
+    or None, u8 or None, new memory (2, H, W))`` with ``E`` the number of emitting steps, in step order (both ``None`` when no step
+    emits) -- bit for bit what a loop of ``encode_sae_dat`` gives.  ``ValueError`` outside 1..64 steps, for a step tuple of another
+    length, a range that runs backwards or leaves ``dat``, too many lamdas; ``NotImplementedError``: shape outside the path.
+    ``check`` as for ``encode_sae_batch``.  Integer atomics: no dependence on the LDS lane-order self-test."""
+    H, W = int(shape[0]), int(shape[1])
+    steps = [tuple(s) for s in steps]
+    S = len(steps)
+    if S < 1 or S > _lib.MAX_SEQUENCES:
+        raise ValueError(f"1..{_lib.MAX_SEQUENCES} steps per call")
+    if any(len(s) != 5 for s in steps):
+        raise ValueError("a step is (lo, hi, now, window_us, emit)")
+    if len(lamdas) > _lib.MAX_LAMDAS:
+        raise ValueError(f"at most {_lib.MAX_LAMDAS} lamdas")
+    n = dat.numel() * dat.element_size() // 8
+    for lo, hi, _, _, _ in steps:
+        if int(lo) < 0 or int(hi) < int(lo) or int(hi) > n:
+            raise ValueError(f"record range ({lo}, {hi}) outside 0 <= lo <= hi <= {n}")
+    if memory is not None and tuple(memory.shape) != (2, H, W):
+        raise ValueError(f"memory must be (2, {H}, {W})")
+    E = sum(1 for s in steps if s[4])
+    if E and not want_f32 and not want_u8:
+        raise ValueError("nothing to return: want_f32 or want_u8")
+    d, desc = _events_dat(dat, xmap, ymap)
+    need = _lib.load().frlw_sae_chain_workspace_bytes(n, S, H, W)
+    if need == 0:
+        raise NotImplementedError("shape outside the chained Surface of Active Events path")
+    ws = _slot_workspace(need, d.device, "sae_chain")
+    L = len(lamdas)
+    lam = (C.c_double * max(L, 1))(*[float(l) for l in lamdas])
+    out = torch.empty((E, 2 * L, H, W), dtype=torch.float32, device=d.device) if (want_f32 and E) else None
+    u8 = torch.empty((E, 2 * L, H, W), dtype=torch.uint8, device=d.device) if (want_u8 and E) else None
+    mem_out = torch.empty((2, H, W), dtype=torch.float32, device=d.device)
+    mem_in = None if memory is None else memory.to(torch.float32).contiguous()
+    col = lambda k: (C.c_int64 * S)(*[int(s[k]) for s in steps])  # noqa: E731
+    rc = _lib.load().frlw_sae_encode_chain(C.byref(desc), col(0), col(1), col(2), col(3), (C.c_uint8 * S)(*[1 if s[4] else 0 for s in steps]),
+                                           S, H, W, lam, L, _ptr(mem_in), _ptr(mem_out), _ptr(out), _ptr(u8), _ptr(ws), ws.numel(),
+                                           _stream())
+    if rc == _lib.FRLW_ERR_UNSUPPORTED:
+        raise NotImplementedError("input outside the chained Surface of Active Events path")
+    _lib.check(rc, "encode_sae_chain")
+    if check:
+        _finish(ws, "encode_sae_chain")
     return out, u8, mem_out

@@ -96,52 +96,127 @@ def generate_eventcountimage(raw_dir, label_dir, target_dir, dataset="gen4", dev
 
 
 # ---- generate_eventvolume.py:63-172 -------------------------------------------------------------------------------------
+EV_TIME_WINDOWS = [250000, 500000, 1000000]
+# Gathered records per encode_ev_ranges call: the call copies its windows' records (8 bytes each) and partitions the copy (two
+# 4-byte record arrays), so 4 M records bound the workspace at about 64 MB plus the per-window tables -- and 64 one-second GEN1
+# label windows (some 125 000 events each in the test recordings) still fit one call.  A single window above it goes alone.
+EV_RECORD_BUDGET = 4_000_000
+
+
+def ev_jobs(slices, tw, prefix, times=None):
+    """The Event Volume jobs of one file and one time window ``tw``, in label order: ``(lo, hi, end_time, path)`` per slice of
+    ``dat_io.ev_label_slices`` -- records ``[lo, hi)``, window end, output file ``<prefix>_<label_time>.npy``.  ``times``: the
+    file's time column on the host (time-sorted, as every bisection of ``DatFile`` assumes); with it ``lo`` moves up to the first
+    record with ``t > end_time - tw`` -- the encoder drops the records in front of it anyway (:139), so they need not be copied."""
+    jobs = []
+    for sl in slices:
+        lo, hi, end = int(sl["start_count"]), int(sl["end_count"]), int(sl["end_time"])
+        if times is not None and end - tw >= 0 and hi > lo:
+            lo += int(np.searchsorted(times[lo:hi], end - tw, side="right"))
+        jobs.append((lo, hi, end, f"{prefix}_{sl['label_time']}.npy"))
+    return jobs
+
+
+def ev_parts(jobs, max_windows=er._lib.MAX_SEQUENCES, budget=EV_RECORD_BUDGET):
+    """``jobs`` cut, in order, into the parts one ``encode_ev_ranges`` call takes: at most ``max_windows`` windows and at most
+    ``budget`` gathered records (a single job above the budget is a part of its own)."""
+    parts, cur, held = [], [], 0
+    for job in jobs:
+        n = job[1] - job[0]
+        if cur and (len(cur) >= max_windows or held + n > budget):
+            parts.append(cur)
+            cur, held = [], 0
+        cur.append(job)
+        held += n
+    if cur:
+        parts.append(cur)
+    return parts
+
+
+def _eventvolume_loop(dat, part, enc, tw, bins, xmap, ymap):
+    """One call and one synchronisation per window: what the command did before encode_ev_ranges, and still does for a part the
+    ranged path does not take (a window of 2^20 us or more, a frame with too many tiles, a device that failed the self-test)."""
+    # events with t > end_time - tw, t* = (t - (end_time - tw)) / tw (:139-141); > 255 -> 255, uint8 (:155-157)
+    return [er.encode_ev_dat(dat[lo:hi], enc, end, tw, bins, want_f32=False, want_u8=True, xmap=xmap, ymap=ymap)[1]
+            for lo, hi, end, _ in part]
+
+
 def generate_eventvolume(raw_dir, label_dir, target_dir, dataset="gen1", device="cuda"):
-    time_windows = [250000, 500000, 1000000]
+    time_windows = EV_TIME_WINDOWS
     bins = 5
     _, target, enc, xmap, ymap = _geometry(dataset, device)
     os.makedirs(target_dir, exist_ok=True)
     n_files = 0
-    # (one call per label window: the label slices of a file overlap, which encode_ev_batch's contiguous partition of the record
-    # array cannot express)
     for mode, name, event_file, bbox_file in _sequences(raw_dir, label_dir):
         f_event = dat_io.DatFile(event_file)
         dat = f_event.to_device(device=device)
-        for sl in dat_io.ev_label_slices(f_event, read_label_times(bbox_file), time_windows):
-            rec = dat[sl["start_count"]:sl["end_count"]]
-            for tw in time_windows:
-                # events with t > end_time - tw, t* = (t - (end_time - tw)) / tw (:139-141); > 255 -> 255, uint8 (:155-157)
-                _, u8 = er.encode_ev_dat(rec, enc, sl["end_time"], tw, bins, want_f32=False, want_u8=True, xmap=xmap, ymap=ymap)
-                _write(u8, enc, target, os.path.join(target_dir, f"EventVolume{tw}", mode, f"{name}_{sl['label_time']}.npy"))
-                n_files += 1
+        # the label slices of a file overlap (each reaches max(time_windows) back), so a window is a record RANGE of `dat`: the
+        # ranges of one time window go through encode_ev_ranges, up to 64 per call, instead of one call and one synchronisation each
+        slices = list(dat_io.ev_label_slices(f_event, read_label_times(bbox_file), time_windows))
+        for tw in time_windows:
+            jobs = ev_jobs(slices, tw, os.path.join(target_dir, f"EventVolume{tw}", mode, name), f_event._t)
+            max_windows = er.ev_ranges_max_windows(enc, tw)
+            for part in ev_parts(jobs, max(max_windows, 1)):
+                try:
+                    if max_windows == 0:
+                        raise NotImplementedError
+                    _, u8 = er.encode_ev_ranges(dat, [(lo, hi) for lo, hi, _, _ in part], enc, [end for _, _, end, _ in part], tw, bins,
+                                                want_f32=False, want_u8=True, xmap=xmap, ymap=ymap)
+                except NotImplementedError:
+                    u8 = _eventvolume_loop(dat, part, enc, tw, bins, xmap, ymap)
+                for b, (_, _, _, path) in enumerate(part):
+                    _write(u8[b], enc, target, path)
+                    n_files += 1
     return n_files
 
 
 # ---- generate_surfaceofactiveevents.py:82-215 ---------------------------------------------------------------------------
+SAE_LAMDAS = [0.00001, 0.0000025, 0.000001]
+SAE_TIME_WINDOWS = [554126, 2216505, 5541263]
+
+
+def sae_steps(slices, mode, time_window=SAE_TIME_WINDOWS):
+    """The chain of one file, in label order: ``(lo, hi, now, window_us, emit)`` per slice of ``dat_io.sae_label_slices`` and
+    window.  The test split runs all of ``time_window`` on a label, each on the memory the previous one left (:178-194), the other
+    splits only the largest; ``now`` is the label time, and only the last window of a label emits -- the volume the file keeps
+    (:199-200)."""
+    windows = list(time_window) if mode == "test" else [max(time_window)]
+    steps = []
+    for sl in slices:
+        for j, tw in enumerate(windows):
+            steps.append((int(sl["start_count"]), int(sl["end_count"]), int(sl["label_time"]), int(tw), j == len(windows) - 1))
+    return steps
+
+
+def sae_parts(steps, max_steps=er._lib.MAX_SEQUENCES):
+    """``steps`` in parts of at most ``max_steps``, what one ``encode_sae_chain`` call takes (a part may end between the steps of
+    one label: the memory carries over)."""
+    return [steps[i:i + max_steps] for i in range(0, len(steps), max_steps)]
+
+
 def generate_surfaceofactiveevents(raw_dir, label_dir, target_dir, dataset="gen1", device="cuda"):
-    lamdas = [0.00001, 0.0000025, 0.000001]
-    time_window = [554126, 2216505, 5541263]
+    lamdas = SAE_LAMDAS
     _, target, enc, xmap, ymap = _geometry(dataset, device)
     os.makedirs(target_dir, exist_ok=True)
     n_files = 0
     for mode, name, event_file, bbox_file in _sequences(raw_dir, label_dir):
         f_event = dat_io.DatFile(event_file)
         dat = f_event.to_device(device=device)
-        memory = None   # carried from label to label within a file: the labels are a chain, not a batch (encode_sae_batch is for
-        # independent streams), so this loop stays one call per label
-        for sl in dat_io.sae_label_slices(f_event, read_label_times(bbox_file)):
-            rec = dat[sl["start_count"]:sl["end_count"]]
-            # the test split runs all three windows, each on the memory the previous one left (:178-194); the file holds the
-            # volume of the largest window (:199-200)
-            u8 = None
-            for tw in (time_window if mode == "test" else [max(time_window)]):
-                _, u8, memory = er.encode_sae_dat(rec, enc, lamdas, memory, sl["label_time"], tw, want_f32=False, want_u8=True,
-                                                  xmap=xmap, ymap=ymap)
-            vol = u8.view(len(lamdas), 2, enc[0], enc[1])
-            for j, lam in enumerate(lamdas):
-                _write(vol[j], enc, target, os.path.join(target_dir, f"SurfaceOfActiveEvents{lam}", mode,
-                                                         f"{name}_{sl['label_time']}.npy"))
-                n_files += 1
+        # the labels of a file are a chain -- the per-pixel memory goes from label to label -- which encode_sae_chain runs as one
+        # call per 64 steps; the memory is carried from part to part and starts anew with every file
+        memory = None
+        steps = sae_steps(dat_io.sae_label_slices(f_event, read_label_times(bbox_file)), mode)
+        for part in sae_parts(steps):
+            _, u8, memory = er.encode_sae_chain(dat, part, enc, lamdas, memory, want_f32=False, want_u8=True, xmap=xmap, ymap=ymap)
+            emitted = 0
+            for _, _, label_time, _, emit in part:
+                if not emit:
+                    continue
+                vol = u8[emitted].view(len(lamdas), 2, enc[0], enc[1])
+                emitted += 1
+                for j, lam in enumerate(lamdas):
+                    _write(vol[j], enc, target, os.path.join(target_dir, f"SurfaceOfActiveEvents{lam}", mode, f"{name}_{label_time}.npy"))
+                    n_files += 1
     return n_files
 
 

@@ -283,6 +283,44 @@ int frlw_sae_encode_batch(const frlw_events_t *ev, const int64_t *seq_offsets, c
  * frlw_eci_encode_batch, counts[1] = frlw_sae_encode_batch (host-side: ENQUEUES, the replays of a captured graph add nothing). */
 int frlw_encoder_batch_counts(uint64_t counts[2]);
 
+/*
+ * Surface of Active Events for a CHAIN of steps on ONE memory plane (csrc/encoders_batch.hip) -- the labels of one file of the
+ * offline command (generate_surfaceofactiveevents.py:147-200), whose per-pixel memory goes from label to label.  Step s encodes the
+ * DAT8 records [step_lo[s], step_hi[s]) with its own now[s] and window_us[s] (window_us[s] <= 0 keeps every event); ranges may
+ * overlap, nest, repeat or be empty.  All five arrays are HOST arrays of n_steps <= FRLW_MAX_SEQUENCES entries.  mem_in (2, H, W)
+ * is what step 0 starts from (NULL = no memory yet, as for frlw_sae_encode), step s + 1 starts from what step s left, mem_out
+ * receives what the last step left; the two may alias.  A step with emit[s] != 0 writes its volume, the others only advance the
+ * memory: the emitting steps are packed in step order into out_f32 and / or out_u8, (n_emit, 2 * n_lamda, H, W); no emitting step
+ * and both outputs NULL is legal.  Bit-identical -- memory, f32 and u8 -- to n_steps successive calls of frlw_sae_encode, each on
+ * its range and fed the previous call's memory.  Three launches, no host synchronisation.  A coordinate outside the maps is
+ * reported by frlw_encoder_status() as FRLW_ERR_INDEX.  Workspace: frlw_sae_chain_workspace_bytes (one 64-bit key plane per step,
+ * what frlw_sae_batch_workspace_bytes asks for as many sequences); 0 = n_steps outside 1..FRLW_MAX_SEQUENCES or an unsupported shape.
+ */
+size_t frlw_sae_chain_workspace_bytes(int64_t n_records, int n_steps, int H, int W);
+int frlw_sae_encode_chain(const frlw_events_t *ev, const int64_t *step_lo, const int64_t *step_hi, const int64_t *now,
+                          const int64_t *window_us, const uint8_t *emit, int n_steps, int H, int W, const double *lamdas, int n_lamda,
+                          const float *mem_in, float *mem_out, float *out_f32, uint8_t *out_u8, void *workspace,
+                          size_t workspace_bytes, frlw_stream_t stream);
+
+/*
+ * Event Volume for label windows given as RECORD RANGES (csrc/taf_fast.hip): window w is the DAT8 records [win_lo[w], win_hi[w])
+ * of ev->data and ends at t_end[w] (HOST arrays, n_win <= FRLW_MAX_SEQUENCES); windows may overlap, nest or be empty -- the label
+ * slices of one file (generate_eventvolume.py:118-137).  One launch copies the ranges one behind the other into the workspace
+ * (n_gathered = the sum of the range lengths), then the code of frlw_ev_encode_batch runs on the copy: its contract holds
+ * (bit-identical to n_win calls of frlw_ev_encode; DAT8 only; window_us < 2^20; an event behind its t_end is FRLW_ERR_SPAN and
+ * nothing is written; FRLW_ERR_UNSUPPORTED where the batch call answers it).  Workspace: frlw_ev_ranges_workspace_bytes =
+ * frlw_ev_batch_workspace_bytes(n_gathered, ...) rounded up, which lies in FRONT (the workspace header stays the status header),
+ * plus 8 bytes per gathered record behind it; 0 = unsupported.
+ */
+size_t frlw_ev_ranges_workspace_bytes(int64_t n_gathered, int n_win, int H, int W, int64_t window_us);
+int frlw_ev_encode_ranges(const frlw_events_t *ev, const int64_t *win_lo, const int64_t *win_hi, const int64_t *t_end, int n_win,
+                          int H, int W, int bins, int64_t window_us, float *out_f32, uint8_t *out_u8, void *workspace,
+                          size_t workspace_bytes, frlw_stream_t stream);
+
+/* Calls served by the two entry points above, like frlw_encoder_batch_counts: counts[0] = frlw_sae_encode_chain, counts[1] =
+ * frlw_ev_encode_ranges (host-side: ENQUEUES). */
+int frlw_encoder_chain_counts(uint64_t counts[2]);
+
 /* The verdict of the one-time LDS lane-order self-test of the fast paths (frlw_taf_encode_batch, frlw_ev_encode_batch, the
  * two-launch forms of frlw_sae_encode / frlw_eci_encode) for the CURRENT device: *ok_out = 1 when the property held, 0 when
  * it did not (those entry points then answer FRLW_ERR_UNSUPPORTED and callers take the general path -- same bits, different

@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
-"""Timings of the batched Event Count Image / Surface of Active Events encoders against the single calls they replace, same
-box, same run, one JSON line each:
+"""Timings of the batched Event Count Image / Surface of Active Events encoders and of the per-file label calls against the
+single calls they replace, same box, same run, one JSON line each:
 
-  eci   64 windows x 100 000 events at 304x240: one encode_eci_batch against 64 encode_eci_dat calls
-  sae   64 streams x 1 000 000 events, 3 lamdas:  one encode_sae_batch against 64 encode_sae_dat calls
+  eci     64 windows x 100 000 events at 304x240: one encode_eci_batch against 64 encode_eci_dat calls
+  sae     64 streams x 1 000 000 events, 3 lamdas:  one encode_sae_batch against 64 encode_sae_dat calls
+  chain   64 chained steps x 100 000 events, 3 lamdas: one encode_sae_chain against 64 encode_sae_dat calls fed their memory
+  ranges  64 overlapping windows x 100 000 events (each starts 25 000 records after the one before), 5 bins: one
+          encode_ev_ranges against 64 encode_ev_dat calls
 
 Device events around `n` back-to-back repetitions, `--runs` (>= 5) such regions after a warm-up; the value is the median, the
 spread min .. max.  Both sides are timed unchecked (``check=False``: no host synchronisation, the device's best case for the
@@ -11,7 +14,7 @@ single calls) and checked (their default).  GB/s = 8 bytes per record plus the p
 batched call's time.  Each side runs in a child process of its own under a time limit; the parent never opens the GPU and
 starts nothing more after a child that did not end normally.
 
-``python tools/time_batch_encoders.py [--runs 7] [--out profiles/eci_sae_batch_time.txt]``
+``python tools/time_batch_encoders.py [--runs 7] [--sides chain,ranges] [--out profiles/label_batches_time.txt]``
 """
 import argparse
 import json
@@ -24,7 +27,7 @@ sys.path.insert(0, ROOT)
 
 H, W, B = 240, 304, 64
 LAMDAS = [0.00001, 0.0000025, 0.000001]
-LIMIT_S = {"eci": 240, "sae": 420}
+LIMIT_S = {"eci": 240, "sae": 420, "chain": 240, "ranges": 240}
 
 
 def regions(fn, runs, n, warm=2):
@@ -118,10 +121,77 @@ def side_sae(runs):
           flush=True)
 
 
+def side_chain(runs):
+    import torch
+    from frlw_evd_amd import event_representation as er
+    n = 100_000
+    win = 800_000
+    dat = streams(16, n, 300, t_offset=10_000_000)
+    steps = [(s * n, (s + 1) * n, 11_000_500 + 1_000 * s, win, True) for s in range(B)]   # every step emits its volume
+    mem = torch.full((2, H, W), 9_000_000.0, device="cuda")
+
+    def single(check):
+        m, out = mem, None
+        for lo, hi, now, w, _ in steps:
+            out, _, m = er.encode_sae_dat(dat[lo:hi], (H, W), LAMDAS, m, now, w, check=check)
+        return out, m
+
+    f32, _, m = er.encode_sae_chain(dat, steps, (H, W), LAMDAS, mem)
+    f1, m1 = single(True)
+    assert torch.equal(f32[B - 1], f1) and torch.equal(m, m1)
+    nbytes = B * n * 8 + 2 * H * W * 4 * (2 + B * len(LAMDAS)) + B * 2 * H * W * 8   # records, memory, the f32 decays, the key planes
+    res = {}
+    for check in (False, True):
+        tag = "checked" if check else "unchecked"
+        res["b", check] = report(f"sae chain: 1 call, {B} steps x {n} events, {tag}",
+                                 regions(lambda: er.encode_sae_chain(dat, steps, (H, W), LAMDAS, mem, check=check), runs, 10))
+        res["s", check] = report(f"sae single: {B} chained calls x {n} events, {tag}", regions(lambda: single(check), runs, 3))
+        er.raise_deferred()
+    print(json.dumps({"what": "sae chain: one call / 64 single calls", "ratio_unchecked": round(res["b", False] / res["s", False], 4),
+                      "ratio_checked": round(res["b", True] / res["s", True], 4), "bytes": nbytes,
+                      "chain_GB_per_s": round(nbytes / res["b", False] / 1e6, 1),
+                      "us_per_step_chained": round(res["b", False] * 1e3 / B, 2), "us_per_single_call": round(res["s", False] * 1e3 / B, 2)}),
+          flush=True)
+
+
+def side_ranges(runs):
+    import numpy as np
+    import torch
+    from frlw_evd_amd import event_representation as er, synth
+    n, hop, win, bins = 100_000, 25_000, 250_000, 5
+    total = (B - 1) * hop + n
+    rec = synth.to_dat8(synth.synth_events(400, total, W, H, win * total // n, hotspot=True, t_offset=win + 1))   # a window's 100 000 records span about `win`
+    dat = torch.from_numpy(rec.view(np.uint8).reshape(-1, 8).copy()).cuda()
+    ranges = [(s * hop, s * hop + n) for s in range(B)]
+    t_end = [int(rec["t"][hi - 1]) for _, hi in ranges]
+    parts = [dat[lo:hi] for lo, hi in ranges]
+    f32, _ = er.encode_ev_ranges(dat, ranges, (H, W), t_end, win, bins)
+    for s in (0, 1, B - 1):
+        assert torch.equal(f32[s], er.encode_ev_dat(parts[s], (H, W), t_end[s], win, bins)[0])
+    nbytes = 3 * B * n * 8 + B * 2 * bins * H * W * 4   # records read, copied and read again, the f32 volumes
+    res = {}
+    for check in (False, True):
+        tag = "checked" if check else "unchecked"
+        res["b", check] = report(f"ev ranges: 1 call, {B} windows x {n} events, {tag}",
+                                 regions(lambda: er.encode_ev_ranges(dat, ranges, (H, W), t_end, win, bins, check=check), runs, 10))
+        res["s", check] = report(f"ev single: {B} calls x {n} events, {tag}",
+                                 regions(lambda: [er.encode_ev_dat(parts[s], (H, W), t_end[s], win, bins, check=check) for s in range(B)], runs, 3))
+        er.raise_deferred()
+    print(json.dumps({"what": "ev ranges: one call / 64 single calls", "ratio_unchecked": round(res["b", False] / res["s", False], 4),
+                      "ratio_checked": round(res["b", True] / res["s", True], 4), "bytes": nbytes,
+                      "ranges_GB_per_s": round(nbytes / res["b", False] / 1e6, 1),
+                      "us_per_window_ranged": round(res["b", False] * 1e3 / B, 2), "us_per_single_call": round(res["s", False] * 1e3 / B, 2)}),
+          flush=True)
+
+
+SIDES = {"eci": side_eci, "sae": side_sae, "chain": side_chain, "ranges": side_ranges}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=7)
-    ap.add_argument("--only", choices=("eci", "sae"))
+    ap.add_argument("--only", choices=tuple(SIDES))
+    ap.add_argument("--sides", default=",".join(SIDES), help="comma-separated subset of " + ", ".join(SIDES))
     ap.add_argument("--out")
     a = ap.parse_args()
     assert a.runs >= 5
@@ -129,10 +199,12 @@ def main():
         import torch
         from frlw_evd_amd import _lib
         print(json.dumps({"device": torch.cuda.get_device_name(0), "library": _lib.load().frlw_version().decode(), "side": a.only}), flush=True)
-        {"eci": side_eci, "sae": side_sae}[a.only](a.runs)
+        SIDES[a.only](a.runs)
         return 0
     text = ""
-    for side in ("eci", "sae"):
+    for side in a.sides.split(","):
+        if side not in SIDES:
+            ap.error(f"unknown side {side}")
         try:
             p = subprocess.run([sys.executable, os.path.abspath(__file__), "--only", side, "--runs", str(a.runs)], capture_output=True,
                                text=True, timeout=LIMIT_S[side])
