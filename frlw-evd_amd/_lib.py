@@ -129,6 +129,10 @@ SYMBOLS = {
     "frlw_ev_encode_ranges": (_I, [_EV, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _I, _I, _I, _I, _I64, _P, _P,
                                   _P, _SZ, _P]),
     "frlw_encoder_chain_counts": (_I, [C.POINTER(C.c_uint64)]),
+    "frlw_time_surface_workspace_bytes": (_SZ, [_I64, _I, _I, _I]),
+    "frlw_time_surface_batch": (_I, [_EV, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _I, _I, _I, _P, _P, _P, _SZ, _P]),
+    "frlw_box_flow_sums": (_I, [_P, _I, _I, _I, _P, _I64, _P, _P]),
+    "frlw_motion_counts": (_I, [C.POINTER(C.c_uint64)]),
     "frlw_leaky_transform": (_I, [_P, _I64, _P, _P, _P]),
     "frlw_resize_nearest_f32": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "frlw_resize_nearest_u8": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),

@@ -321,6 +321,40 @@ int frlw_ev_encode_ranges(const frlw_events_t *ev, const int64_t *win_lo, const 
  * frlw_ev_encode_ranges (host-side: ENQUEUES). */
 int frlw_encoder_chain_counts(uint64_t counts[2]);
 
+/*
+ * Time-surface pairs for a batch of record windows (csrc/motion.hip) -- generate_timesurface and its harness lines
+ * (generate_opticalflow.py:72-92, :176-187) for n_win <= FRLW_MAX_SEQUENCES windows in one launch sequence.  Window w is the DAT8
+ * records [win_lo[w], win_hi[w]) of ev->data (HOST arrays of record indices); windows may overlap, nest or be empty.  Events
+ * outside the frame are dropped without error, polarity is ignored.  start / end = the smallest / largest timestamp of the window's
+ * in-bounds events; volume1 keeps per cell the LAST event in stream order with t < end - 50000, volume2 the last of all;
+ * out_u8 (n_win, 2, H, W) = uint8((v1 - start) / den * 255), uint8((v2 - start - 50000) / den * 255) with den = end - 50000 - start,
+ * in float64 and in that operation order, untouched cells 0 before the subtraction, negative values 0: byte for byte the
+ * reference's pair.  A window without an in-bounds event gives zeros.  A window with den <= 0 (its events span 50 ms or less) is
+ * NOT computed -- the reference divides by zero or a negative number there and numpy's cast decides -- zeros are stored and the
+ * caller recomputes it; stamps_out (DEVICE, n_win x 2 int64, or NULL) receives start and end of every window (-1, -1: none) to tell.
+ * Four launches, no host synchronisation.  DAT8 only, no coordinate maps (FRLW_ERR_UNSUPPORTED).  Workspace:
+ * frlw_time_surface_workspace_bytes (two 64-bit key planes per window); 0 = n_win outside 1..FRLW_MAX_SEQUENCES or an unsupported
+ * shape.  A range running backwards / outside the array: FRLW_ERR_ARG.
+ */
+size_t frlw_time_surface_workspace_bytes(int64_t n_records, int n_win, int H, int W);
+int frlw_time_surface_batch(const frlw_events_t *ev, const int64_t *win_lo, const int64_t *win_hi, int n_win, int H, int W,
+                            uint8_t *out_u8, int64_t *stamps_out, void *workspace, size_t workspace_bytes, frlw_stream_t stream);
+
+/*
+ * Sum of the flow magnitude over boxes (csrc/motion.hip) -- np.sum(np.sqrt(flow[y0:y1, x0:x1, 0]**2 + flow[y0:y1, x0:x1, 1]**2))
+ * of motion_level_statistics_gt.py:130 for n_boxes boxes in one launch.  flows: DEVICE (n_flows, H, W, 2) float32, 8-byte aligned;
+ * boxes: DEVICE (n_boxes, 5) int32 rows [flow index, x0, x1, y0, y1]; out: DEVICE (n_boxes) float64.  The magnitude is float32
+ * with every operation rounded on its own (numpy's values exactly), the sum float64 in a fixed order: deterministic, and within
+ * n * 2^-53 (relative) of any other float64 summation order.  An empty box (x0 >= x1 or y0 >= y1) gives 0; a box that leaves the
+ * frame or names a flow outside the batch gives NaN and reads nothing.
+ */
+int frlw_box_flow_sums(const float *flows, int n_flows, int H, int W, const int32_t *boxes, int64_t n_boxes, double *out,
+                       frlw_stream_t stream);
+
+/* Calls served by the two entry points above, like frlw_encoder_batch_counts: counts[0] = frlw_time_surface_batch, counts[1] =
+ * frlw_box_flow_sums (host-side: ENQUEUES). */
+int frlw_motion_counts(uint64_t counts[2]);
+
 /* The verdict of the one-time LDS lane-order self-test of the fast paths (frlw_taf_encode_batch, frlw_ev_encode_batch, the
  * two-launch forms of frlw_sae_encode / frlw_eci_encode) for the CURRENT device: *ok_out = 1 when the property held, 0 when
  * it did not (those entry points then answer FRLW_ERR_UNSUPPORTED and callers take the general path -- same bits, different
