@@ -1,0 +1,78 @@
+#!/usr/bin/env python3
+"""Detect on a raw recording: ``--dat <file>_td.dat`` -> ``<out>.npy``, a structured box array with the fields of a
+``*_bbox.npy`` annotation file (``dataset.read_boxes`` reads it back), one set of boxes every ``--period`` microseconds.
+
+The model is built the way ``test.py`` builds it (``--exp_type``, ``--dataset``, ``--event_volume_bins``; ``--resume_exp E`` loads
+``<log_path>E/checkpoints/best_epoch.pth``, ``--checkpoint`` any checkpoint file of this build or of the reference).  The events
+are encoded on the GPU as the TAF recipes expect them (``generate_taf.py``: K = 8, 10 ms windows) -- every frame of a detector
+batch in one encode call (``frlw_evd_amd.stream.StreamDetector``); no annotation file and no representation file is needed."""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+
+def build_parser():
+    parser = argparse.ArgumentParser(description="Detect on a raw .dat recording.")
+    parser.add_argument("--dat", required=True)          # <sequence>_td.dat
+    parser.add_argument("--out", required=True)          # written as <out>.npy
+    parser.add_argument("--local_rank", "--local-rank", type=int, default=None)
+    parser.add_argument("--resume_exp")
+    parser.add_argument("--checkpoint")                  # a checkpoint file, instead of --resume_exp
+    parser.add_argument("--exp_type", default="yolox_taf_bfm")
+    parser.add_argument("--log_path", default="log/")
+    parser.add_argument("--dataset", default="gen1")
+    parser.add_argument("--event_volume_bins", type=int, default=8)
+    parser.add_argument("--period", type=int, default=50000)          # microseconds between frames
+    parser.add_argument("--frames_per_call", type=int, default=32)
+    parser.add_argument("--t_begin", type=int, default=0)
+    parser.add_argument("--t_end", type=int, default=None)            # default: the last event
+    parser.set_defaults(record=None, bbox_path=None, data_path=None, batch_size=1, num_cpu_workers=1, nodes=1, metric="none")
+    return parser
+
+
+def build_model(args):
+    """The experiment's network as ``test.py`` builds it (``Setting_test`` -> ``_build_all`` -> checkpoint), in eval mode."""
+    import train as train_entry
+    cls = train_entry.pick_experiment(args.exp_type)
+    train_entry.init_distributed(args)
+    from frlw_evd_amd.settings import Setting_test
+    settings = Setting_test(args)
+    if args.checkpoint is not None:
+        settings.resume_ckpt_file = args.checkpoint
+    exp = cls(settings)
+    exp.object_classes = exp._classes()
+    exp._build_all()
+    if settings.resume_ckpt_file is not None:
+        exp.loadCheckpointTest(settings.resume_ckpt_file)
+    return exp.model.module.eval(), settings
+
+
+def main(argv=None):
+    import numpy as np
+    import torch
+    args = build_parser().parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("the encoders and the detector run on the GPU: no ROCm device is visible (there is no CPU fallback)")
+    from frlw_evd_amd import dat_io
+    from frlw_evd_amd.generate import SHAPES
+    from frlw_evd_amd.stream import StreamDetector
+    net, settings = build_model(args)
+    sensor, _ = SHAPES["gen4" if args.dataset == "gen4" else "gen1"]
+    f_event = dat_io.DatFile(args.dat)
+    det = StreamDetector(net, sensor, settings.img_size, dataset=args.dataset, volume_bins=8, input_bins=args.event_volume_bins,
+                         period_us=args.period, frames_per_call=args.frames_per_call)
+    t_end = f_event.total_time() if args.t_end is None else args.t_end
+    boxes = det.run(f_event.to_device(device=settings.gpu_device), args.t_begin, t_end)
+    path = args.out if args.out.endswith(".npy") else args.out + ".npy"
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    np.save(path, boxes)
+    print({"frames": len(det.frame_times(args.t_begin, t_end)), "boxes": int(len(boxes)), "out": path})
+    if torch.distributed.is_initialized():
+        torch.distributed.destroy_process_group()
+    return boxes
+
+
+if __name__ == "__main__":
+    main()

@@ -104,6 +104,7 @@ SYMBOLS = {
     "frlw_ev_encode": (_I, [_EV, _I, _I, _I, _I64, _I64, _P, _P, _P, _SZ, _P]),
     "frlw_sae_encode": (_I, [_EV, _I, _I, C.POINTER(C.c_double), _I, _P, _P, _I64, _I64, _P, _P, _P, _SZ, _P]),
     "frlw_taf_encode": (_I, [_EV, _I, _I, _I, _I64, _I64, _I, _P, _P, _P, _I, _P, _SZ, _P]),
+    "frlw_taf_encode_chain": (_I, [_EV, _I, _I, _I, _I64, _I64, _I, C.c_uint64, _P, _P, _I, _P, _SZ, _P]),
     "frlw_selftest_mfma_f32_rate": (_I, [_I, _I, _P, _P, _P]),
     "frlw_selftest_lds_atomic_order": (_I, [_I, _I, _P, _P]),
     "frlw_fast_path_verdict": (_I, [_P, _SZ, _P, C.POINTER(C.c_int)]),

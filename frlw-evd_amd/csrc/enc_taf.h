@@ -1,4 +1,5 @@
-// enc_taf.h -- TAF: TafParams, the tile body (window-sorted fast loop, window-interleaved general loop, fused write-out) and k_taf_tile.
+// enc_taf.h -- TAF: TafParams, the tile body (window-sorted fast loop, window-interleaved general loop, fused write-out), k_taf_tile
+// and k_taf_tile_snap (the same body, which also writes a uint8 snapshot after chosen windows: frlw_taf_encode_chain).
 // Expects enc_tile.h (Owner, slice_sort, segments_order, the hot-tile list), taf_fifo.h (the FIFO step) and leaky.h (the uint8 look-up).
 #pragma once
 #include "enc_tile.h"
@@ -12,9 +13,13 @@ struct TafParams {
     float *state;    // (H, W, 2, K)
     float *view_f32; // (2K, H, W) or NULL
     uint8_t *out_u8; // (K, 2, H, W) or NULL
+    unsigned long long emit_mask; // k_taf_tile_snap: bit w = a snapshot after window w
+    uint8_t *snap_u8;             // k_taf_tile_snap: (popcount(emit_mask), K, 2, H, W), in window order
 };
 
-template <int NT, int C>
+// SNAP: close_window(w) also writes the uint8 volume of the thread's cells into snapshot popcount(emit_mask below bit w) when bit
+// w of emit_mask is set -- what the write-out would give if the call ended after window w.
+template <int NT, int C, bool SNAP>
 __device__ __forceinline__ void taf_tile_body(const uint2 *rec, const uint32_t *base, const TafParams &q, int tile,
                                               int j0, uint32_t *cnt, uint2 *slot, uint32_t *red, uint32_t *thr)
 {
@@ -53,7 +58,8 @@ __device__ __forceinline__ void taf_tile_body(const uint2 *rec, const uint32_t *
         }
     };
     // closes window w for the thread's cells: FIFO step (skipped when the window is empty in the whole
-    // frame, generate_taf.py:40-41), accumulators back to zero
+    // frame, generate_taf.py:40-41), accumulators back to zero.  SNAP: then the snapshot, if window w emits one (an empty
+    // window emits too: the volume of the window before it)
     auto close_window = [&](int w) {
         const bool has = (wmask >> w) & 1ull;
 #pragma unroll
@@ -61,6 +67,31 @@ __device__ __forceinline__ void taf_tile_body(const uint2 *rec, const uint32_t *
             if (has) fifo_step(st[j], K, true, num[j], fifo_mean(num[j], sum[j]));
             sum[j] = 0.0f;
             num[j] = 0u;
+        }
+        if constexpr (SNAP) {
+            if ((q.emit_mask >> w) & 1ull) {
+                const long long plane = (long long)q.H * q.W;
+                uint8_t *dst = q.snap_u8 + (long long)__popcll(q.emit_mask & ((1ull << w) - 1ull)) * (2 * K) * plane;
+#pragma unroll
+                for (int j = 0; j < C; ++j) {
+                    if (!ow.ok[j]) continue;
+                    // half a cell at a time: the look-up's guesses and table pairs of four slots are all that lives beside
+                    // st[][] and the loop's counters (eight at once spill at NT = 1024, 128 VGPRs)
+#pragma unroll
+                    for (int k0 = 0; k0 < kMaxK; k0 += 4) {
+                        const float v[4] = {st[j][k0], st[j][k0 + 1], st[j][k0 + 2], st[j][k0 + 3]};
+                        uint8_t lv[4];
+                        leaky_u8_lookup_n<4>(v, thr, lv);
+#pragma unroll
+                        for (int k = k0; k < k0 + 4; ++k) {
+                            if (k < K) {
+                                const int ko = q.flip ? (K - 1 - k) : k;
+                                dst[(long long)(2 * ko + ow.p) * plane + ow.pix[j]] = lv[k - k0];
+                            }
+                        }
+                    }
+                }
+            }
         }
     };
 
@@ -119,8 +150,9 @@ __device__ __forceinline__ void taf_tile_body(const uint2 *rec, const uint32_t *
         for (; cur_w < q.n_windows; ++cur_w) close_window(cur_w);
         PROF_MARK(7);
     } else {
-        // ---- general path (stream not time-sorted): nothing has been written yet.  One pass per window
-        // over the whole list, slices in list order, records selected by window.
+        // ---- general path (stream not time-sorted): the state has not been written yet; the snapshots the abandoned loop
+        // wrote (SNAP) are all written again below, every window being closed once more.  One pass per window over the whole
+        // list, slices in list order, records selected by window.
         __syncthreads();
         if (t == 0) atomicAdd(&q.hdr->pad, 1u); // diagnostic: tiles on the general path
         load_state();
@@ -184,17 +216,40 @@ __global__ __launch_bounds__(NT) void k_taf_tile(const uint2 *rec, const uint32_
     __shared__ uint32_t red[48];
     __shared__ uint32_t thr[kLeakyLevels];
     if (n_tiles < 0) { // small frame (-n_tiles tiles): every tile as four quarters, grid = 4 * tiles
-        taf_tile_body<NT, 1>(rec, base, q, (int)blockIdx.x >> 2, (int)blockIdx.x & 3, cnt, slot, red, thr);
+        taf_tile_body<NT, 1, false>(rec, base, q, (int)blockIdx.x >> 2, (int)blockIdx.x & 3, cnt, slot, red, thr);
         return;
     }
     if ((int)blockIdx.x >= 4 * kMaxHot) {
         const int tile = (int)blockIdx.x - 4 * kMaxHot;
         if (tile_is_listed(q.hdr, base, tile)) return; // hot: left to its quarters
-        taf_tile_body<NT, CPT>(rec, base, q, tile, 0, cnt, slot, red, thr);
+        taf_tile_body<NT, CPT, false>(rec, base, q, tile, 0, cnt, slot, red, thr);
     } else { // the long-running workgroups come first in the grid
         int tile, quarter;
         if (!pick_quarter(q.hdr, (int)blockIdx.x, tile, quarter)) return;
-        taf_tile_body<NT, 1>(rec, base, q, tile, quarter, cnt, slot, red, thr);
+        taf_tile_body<NT, 1, false>(rec, base, q, tile, quarter, cnt, slot, red, thr);
+    }
+}
+
+// k_taf_tile with snapshots (frlw_taf_encode_chain): same grid, same three launch forms
+template <int NT>
+__global__ __launch_bounds__(NT) void k_taf_tile_snap(const uint2 *rec, const uint32_t *base, TafParams q, int n_tiles)
+{
+    __shared__ uint32_t cnt[NT * CPT];
+    __shared__ uint2 slot[slice_records(NT)];
+    __shared__ uint32_t red[48];
+    __shared__ uint32_t thr[kLeakyLevels];
+    if (n_tiles < 0) {
+        taf_tile_body<NT, 1, true>(rec, base, q, (int)blockIdx.x >> 2, (int)blockIdx.x & 3, cnt, slot, red, thr);
+        return;
+    }
+    if ((int)blockIdx.x >= 4 * kMaxHot) {
+        const int tile = (int)blockIdx.x - 4 * kMaxHot;
+        if (tile_is_listed(q.hdr, base, tile)) return;
+        taf_tile_body<NT, CPT, true>(rec, base, q, tile, 0, cnt, slot, red, thr);
+    } else {
+        int tile, quarter;
+        if (!pick_quarter(q.hdr, (int)blockIdx.x, tile, quarter)) return;
+        taf_tile_body<NT, 1, true>(rec, base, q, tile, quarter, cnt, slot, red, thr);
     }
 }
 } // namespace

@@ -208,8 +208,31 @@ int frlw_taf_encode(const frlw_events_t *ev, int H, int W, int K, int64_t t_star
     q.H = H; q.W = W; q.twl = pt.plan.twl; q.tiles_x = pt.plan.tiles_x; q.K = K;
     q.n_windows = n_windows; q.flip = (flags & FRLW_TAF_U8_FLIP_K) ? 1 : 0;
     q.hdr = pt.hdr; q.state = state; q.view_f32 = view_f32; q.out_u8 = out_u8; q.leaky_thr = pt.leaky_thr;
+    q.emit_mask = 0; q.snap_u8 = nullptr;
     const TileGrid g = tile_grid(pt.plan);
     launch_tile([](auto nt) { return k_taf_tile<decltype(nt)::value>; }, pt.plan, g.blocks, s, pt.records, pt.base, q, g.n_tiles_arg);
+    HIP_TRY(hipGetLastError());
+    return FRLW_OK;
+}
+
+int frlw_taf_encode_chain(const frlw_events_t *ev, int H, int W, int K, int64_t t_start, int64_t window_us,
+                          int n_windows, uint64_t emit_mask, float *state, uint8_t *snap_u8, int flags,
+                          void *workspace, size_t workspace_bytes, frlw_stream_t stream)
+{
+    if (!state || !snap_u8 || K < 1 || K > FRLW_MAX_BINS || n_windows < 1 || n_windows > FRLW_MAX_WINDOWS) return FRLW_ERR_ARG;
+    if (emit_mask == 0 || (n_windows < 64 && (emit_mask >> n_windows) != 0)) return FRLW_ERR_ARG;
+    if (!ev || ev->layout != FRLW_LAYOUT_DAT8 || window_us <= 0) return FRLW_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    Partitioned pt;
+    int rc = partition_events(ev, H, W, KIND_TAF, t_start, window_us, n_windows, 0, workspace, workspace_bytes, s, pt);
+    if (rc != FRLW_OK) return rc;
+    TafParams q;
+    q.H = H; q.W = W; q.twl = pt.plan.twl; q.tiles_x = pt.plan.tiles_x; q.K = K;
+    q.n_windows = n_windows; q.flip = (flags & FRLW_TAF_U8_FLIP_K) ? 1 : 0;
+    q.hdr = pt.hdr; q.state = state; q.view_f32 = nullptr; q.out_u8 = nullptr; q.leaky_thr = pt.leaky_thr;
+    q.emit_mask = emit_mask; q.snap_u8 = snap_u8;
+    const TileGrid g = tile_grid(pt.plan);
+    launch_tile([](auto nt) { return k_taf_tile_snap<decltype(nt)::value>; }, pt.plan, g.blocks, s, pt.records, pt.base, q, g.n_tiles_arg);
     HIP_TRY(hipGetLastError());
     return FRLW_OK;
 }

@@ -469,6 +469,67 @@ def encode_taf_label(dat, shape, state, start_time, window_us, bins, volume_bins
     return u8
 
 
+def encode_taf_chain(dat, shape, state, start_time, window_us, bins, volume_bins=8, flip_k=True, xmap=None, ymap=None, check=True):
+    """The TAF volume at several times along ONE stream (``frlw_taf_encode_chain``, csrc/enc_taf.h): ``bins`` is a list of positive
+    window counts, one per step; the time-sorted records ``dat`` of ``[start_time, start_time + sum(bins) * window_us]`` go
+    through ``sum(bins)`` windows and the newest-first uint8 volume is handed out after every step.  ``state`` (H, W, 2, K) is
+    updated in place.  Returns uint8 ``(len(bins), K, 2, H, W)``: volume ``i`` is the state after ``sum(bins[:i + 1])`` windows --
+    bit for bit what ``len(bins)`` calls of ``encode_taf_label`` on the time-cut record ranges give, for one partition, one tile
+    launch and one read of the event list per 64 windows instead of per step.
+
+    One launch takes at most 64 windows: longer chains run in groups of 64 with the state carried, the records cut by time
+    (``searchsorted(..., right=False)``, as ``encode_taf_label`` cuts them); a step longer than 64 windows spans groups and
+    emits only at its end.  An event on a step boundary belongs to the LATER step (the reference's ``z`` column, :197-203); an
+    event at the very end of the chain goes into the last window.  Always the general path (``fast`` has no say here).
+
+    Memory: the snapshots take ``len(bins) * 2K * H * W`` bytes (64 steps of 304x240, K = 8: 75 MB).  With ``check=False``
+    nothing synchronises (a chain of at most 64 windows) and the caller owes a ``raise_deferred()``."""
+    H, W = int(shape[0]), int(shape[1])
+    K = int(volume_bins)
+    bins = [int(b) for b in bins]
+    if not bins or any(b <= 0 for b in bins):
+        raise ValueError("bins: a non-empty list of positive window counts")
+    assert state.dtype == torch.float32 and state.is_contiguous() and tuple(state.shape) == (H, W, 2, K)
+    max_w = 64
+    total = sum(bins)
+    n_groups = (total + max_w - 1) // max_w
+    masks = [0] * n_groups   # per group: bit w = a snapshot after the group's window w
+    end = 0
+    for b in bins:
+        end += b
+        masks[(end - 1) // max_w] |= 1 << ((end - 1) % max_w)
+    rows = dat.contiguous().view(torch.uint8).reshape(-1, 8)
+    n = rows.shape[0]
+    cuts = [0]
+    if n_groups > 1 and n:
+        t = rows.view(torch.int32).reshape(-1, 2)[:, 0].to(torch.int64) & 0xFFFFFFFF
+        bounds = torch.tensor([start_time + g * max_w * window_us for g in range(1, n_groups)], dtype=torch.int64, device=t.device)
+        cuts += [int(c) for c in torch.searchsorted(t, bounds, right=False).tolist()]
+    else:
+        cuts += [0] * (n_groups - 1)
+    cuts.append(n)
+    snaps = torch.empty((len(bins), K, 2, H, W), dtype=torch.uint8, device=rows.device)
+    ws = _workspace(max(cuts[g + 1] - cuts[g] for g in range(n_groups)), H, W, rows.device)
+    flags = _lib.TAF_U8_FLIP_K if flip_k else 0
+    lib = _lib.load()
+    done = 0
+    for g in range(n_groups):
+        d, desc = _events_dat(rows[cuts[g]:cuts[g + 1]], xmap, ymap)
+        nw = min(max_w, total - g * max_w)
+        t0 = int(start_time) + g * max_w * int(window_us)
+        if masks[g]:
+            _lib.check(lib.frlw_taf_encode_chain(C.byref(desc), H, W, K, t0, int(window_us), nw, masks[g], _ptr(state),
+                                                 C.c_void_p(snaps[done].data_ptr()), flags, _ptr(ws), ws.numel(), _stream()),
+                       "encode_taf_chain")
+            done += bin(masks[g]).count("1")
+        else:   # inside a step longer than 64 windows: the state moves, nothing is handed out
+            _lib.check(lib.frlw_taf_encode(C.byref(desc), H, W, K, t0, int(window_us), nw, _ptr(state), None, None, flags,
+                                           _ptr(ws), ws.numel(), _stream()), "encode_taf_chain")
+    if check:
+        _finish(ws, "encode_taf_chain")
+    return snaps
+
+
 def encode_ev_dat(dat, shape, t_end, window_us, volume_bins=5, want_f32=True, want_u8=False, xmap=None, ymap=None,
                   check=True, fast="auto"):
     """generate_eventvolume.py:139-157 on device -> (f32 (2*bins, H, W) or None, u8 or None).

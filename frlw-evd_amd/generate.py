@@ -221,6 +221,43 @@ def generate_surfaceofactiveevents(raw_dir, label_dir, target_dir, dataset="gen1
 
 
 # ---- generate_taf.py:78-243 ---------------------------------------------------------------------------------------------
+def taf_chains(slices, last_time_of, events_window_abin=10000, max_snapshots=er._lib.MAX_SEQUENCES):
+    """The labels of one file (the dicts of ``dat_io.taf_label_slices``, in order) grouped into chains, each a list of slices that
+    one ``encode_taf_chain`` call encodes: the records ``[first start_count, last end_count)`` from the first ``start_time``, one
+    step of ``bins`` windows per label.  ``last_time_of(slice)``: the timestamp of the slice's last record (``end_count - 1``),
+    ``None`` for a slice without records.  Host arithmetic only.
+
+    A label joins the running chain only if ALL of these hold; anything else starts a new chain, and a chain of one label is the
+    per-label call:
+
+    * it is not ``fresh`` (its FIFO state continues the previous label's);
+    * ``bins > 0`` -- a label that rounds onto the previous one is the double-transform branch of ``encode_taf_label``: it needs
+      the state at that point and stays alone, as does a chain's first label;
+    * its ``start_time`` lies on the chain's window grid right behind the windows so far (a label whose predecessor was clipped
+      to ``total_time()`` is off the grid);
+    * the previous label's last record is strictly earlier than that label's ``end_time``: ``DatFile.seek_time`` can land inside
+      a run of equal timestamps, whose earlier part the per-label call clamps into the label's last window -- the chain would
+      move it to the next window;
+    * the chain holds fewer than ``max_snapshots`` labels."""
+    chains, cur, windows = [], [], 0
+    for sl in slices:
+        join = bool(cur) and not sl["fresh"] and sl["bins"] > 0 and cur[-1]["bins"] > 0 and len(cur) < max_snapshots
+        if join:
+            join = sl["start_time"] == cur[0]["start_time"] + windows * events_window_abin and sl["start_count"] == cur[-1]["end_count"]
+        if join:
+            last = last_time_of(cur[-1])
+            join = last is None or last < cur[-1]["end_time"]
+        if not join:
+            if cur:
+                chains.append(cur)
+            cur, windows = [], 0
+        cur.append(sl)
+        windows += max(sl["bins"], 0)
+    if cur:
+        chains.append(cur)
+    return chains
+
+
 def generate_taf(raw_dir, label_dir, target_dir, dataset="gen4", device="cuda"):
     events_window_abin, K, min_event_count = 10000, 8, 50000000
     _, target, enc, xmap, ymap = _geometry(dataset, device)
@@ -232,23 +269,34 @@ def generate_taf(raw_dir, label_dir, target_dir, dataset="gen4", device="cuda"):
         f_event = dat_io.DatFile(event_file)
         dat = f_event.to_device(device=device)
         state, stale = None, 0
-        for sl in dat_io.taf_label_slices(f_event, read_label_times(bbox_file), events_window_abin, K, min_event_count):
+        slices = list(dat_io.taf_label_slices(f_event, read_label_times(bbox_file), events_window_abin, K, min_event_count))
+        # a run of labels on one window grid is one encode_taf_chain call -- one partition, one tile launch, one synchronisation
+        # -- instead of one encode_taf_label call each; a label alone in its chain takes the per-label call as before
+        chains = taf_chains(slices, lambda sl: int(f_event._t[sl["end_count"] - 1]) if sl["end_count"] > sl["start_count"] else None,
+                            events_window_abin)
+        for chain in chains:
+            sl = chain[0]
             if sl["fresh"]:
                 state = torch.full((enc[0], enc[1], 2, K), -6000.0, device=device)   # :205-209
             # a label that rounds onto the previous one has no window (:181): the reference's `volume` is then STALE -- the
             # previous label's already transformed volume goes through leaky_transform again (:226-227); `stale` counts how
             # many such labels precede this one in a row
             stale = stale + 1 if sl["bins"] <= 0 else 0
-            u8 = er.encode_taf_label(dat[sl["start_count"]:sl["end_count"]], enc, state, sl["start_time"], events_window_abin,
-                                     sl["bins"], K, flip_k=True, xmap=xmap, ymap=ymap, stale_transforms=max(stale - 1, 0))
+            if len(chain) == 1:
+                vols = er.encode_taf_label(dat[sl["start_count"]:sl["end_count"]], enc, state, sl["start_time"], events_window_abin,
+                                           sl["bins"], K, flip_k=True, xmap=xmap, ymap=ymap, stale_transforms=max(stale - 1, 0))[None]
+            else:
+                vols = er.encode_taf_chain(dat[sl["start_count"]:chain[-1]["end_count"]], enc, state, sl["start_time"],
+                                           events_window_abin, [c["bins"] for c in chain], K, flip_k=True, xmap=xmap, ymap=ymap)
             if tuple(enc) != tuple(target):
-                u8 = er.resize_nearest(u8.reshape(2 * K, enc[0], enc[1]), target).reshape(K, 2, target[0], target[1])
-            host = u8.cpu().numpy()
-            for part, sub in ((host[:K // 2], f"bins{K // 2}"), (host[K // 2:], f"bins{K}")):   # :229-235
-                path = os.path.join(target_dir, mode, sub, f"{name}_{sl['label_time']}.npy")
-                os.makedirs(os.path.dirname(path), exist_ok=True)
-                part.tofile(path)
-                n_files += 1
+                vols = er.resize_nearest(vols.reshape(len(chain) * 2 * K, enc[0], enc[1]), target).reshape(len(chain), K, 2, target[0], target[1])
+            vols = vols.cpu().numpy()
+            for host, c in zip(vols, chain):
+                for part, sub in ((host[:K // 2], f"bins{K // 2}"), (host[K // 2:], f"bins{K}")):   # :229-235
+                    path = os.path.join(target_dir, mode, sub, f"{name}_{c['label_time']}.npy")
+                    os.makedirs(os.path.dirname(path), exist_ok=True)
+                    part.tofile(path)
+                    n_files += 1
     return n_files
 
 

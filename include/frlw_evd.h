@@ -190,6 +190,21 @@ int frlw_taf_encode(const frlw_events_t *ev, int H, int W, int K, int64_t t_star
                     frlw_stream_t stream);
 
 /*
+ * Temporal Active Focus with SNAPSHOTS (csrc/enc_taf.h, k_taf_tile_snap) -- frlw_taf_encode on a DAT8 stream that also hands out
+ * the uint8 volume after chosen windows of the same launch: the volumes at several times along one stream for one partition, one
+ * tile launch and one read of the event list.  Bit w of emit_mask (w < n_windows) asks for the volume after window w; snap_u8
+ * (DEVICE, popcount(emit_mask) x (K, 2, H, W)) receives them in window order, each what frlw_taf_encode's out_u8 holds when the
+ * call ends after that window (FRLW_TAF_U8_FLIP_K applies).  A window without any event does not step the FIFO (:40-41) and
+ * still emits: its snapshot equals the one before it.  state is updated in place.  Always the general path; same partition,
+ * workspace (frlw_encoder_workspace_bytes), status word and deferred status as frlw_taf_encode; stream-ordered, no host
+ * synchronisation.  FRLW_ERR_ARG: emit_mask == 0 or a bit at or above n_windows, n_windows outside 1..FRLW_MAX_WINDOWS, state or
+ * snap_u8 NULL, a layout other than DAT8, window_us <= 0.
+ */
+int frlw_taf_encode_chain(const frlw_events_t *ev, int H, int W, int K, int64_t t_start, int64_t window_us,
+                          int n_windows, uint64_t emit_mask, float *state, uint8_t *snap_u8, int flags,
+                          void *workspace, size_t workspace_bytes, frlw_stream_t stream);
+
+/*
  * Temporal Active Focus, fast path for a BATCH of independent sequences (csrc/taf_fast.hip) -- the same harness loop
  * (generate_taf.py:193-235) for n_seq <= FRLW_MAX_SEQUENCES streams in one launch sequence.  Sequence s owns the DAT8
  * records [seq_offsets[s], seq_offsets[s + 1]) of ev->data (HOST array of n_seq + 1 event indices), starts at
