@@ -20,6 +20,7 @@ FRLW_ERR_UNSUPPORTED = -6
 FRLW_ERR_SPAN = -7
 MAX_SEQUENCES = 64
 MAX_LAMDAS = 8
+TVL1_MAX_LEVELS = 8
 
 # the FRLW_CONV_PATH_* counters of frlw_conv_path_counts, in the header's enum order (lower case, prefix dropped)
 CONV_PATHS = ("128x32", "128x128_4x1", "128x128_2x2", "64x128", "64x64", "split_vec", "split_scalar", "split_inkernel",
@@ -57,6 +58,23 @@ class FrlwTuning(C.Structure):
         self.struct_size = C.sizeof(type(self))  # the library reads only what lies inside (frlw_evd.h)
         if kw:
             raise TypeError(f"unknown tuning fields {sorted(kw)}")
+
+
+class FrlwTvl1Params(C.Structure):
+    """frlw_tvl1_params_t: the Dual TV-L1 parameters, OpenCV's defaults (``lam`` is the header's ``lambda``)."""
+    _fields_ = [("struct_size", C.c_int32), ("nscales", C.c_int32), ("warps", C.c_int32), ("inner", C.c_int32), ("outer", C.c_int32),
+                ("median", C.c_int32), ("tau", C.c_float), ("lam", C.c_float), ("theta", C.c_float), ("epsilon", C.c_float),
+                ("scale_step", C.c_float)]
+    DEFAULTS = dict(nscales=5, warps=5, inner=30, outer=10, median=5, tau=0.25, lam=0.15, theta=0.3, epsilon=0.01, scale_step=0.8)
+
+    def __init__(self, **kw):
+        super().__init__()
+        self.struct_size = C.sizeof(type(self))
+        unknown = sorted(set(kw) - set(self.DEFAULTS))
+        if unknown:
+            raise TypeError(f"unknown TV-L1 parameters {unknown}")
+        for name, default in self.DEFAULTS.items():
+            setattr(self, name, type(default)(kw.get(name, default)))
 
 
 class FrlwBaseconvFuse(C.Structure):
@@ -134,6 +152,10 @@ SYMBOLS = {
     "frlw_time_surface_batch": (_I, [_EV, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _I, _I, _I, _P, _P, _P, _SZ, _P]),
     "frlw_box_flow_sums": (_I, [_P, _I, _I, _I, _P, _I64, _P, _P]),
     "frlw_motion_counts": (_I, [C.POINTER(C.c_uint64)]),
+    "frlw_tvl1_plan": (_I, [_I, _I, _I, C.c_double, C.POINTER(C.c_int)]),
+    "frlw_tvl1_workspace_bytes": (_SZ, [_I, _I, _I, _P]),
+    "frlw_tvl1_flow_batch": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _SZ, _P]),
+    "frlw_tvl1_counts": (_I, [C.POINTER(C.c_uint64)]),
     "frlw_leaky_transform": (_I, [_P, _I64, _P, _P, _P]),
     "frlw_resize_nearest_f32": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "frlw_resize_nearest_u8": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),

@@ -3,7 +3,9 @@
 
 * ``time_surface_pairs``: the two time surfaces TV-L1 is run on, for every label window of a file in one launch sequence
   (``frlw_time_surface_batch``, csrc/motion.hip), byte for byte what ``generate_timesurface`` + ``.astype(np.uint8)`` give.  The
-  TV-L1 solver itself stays the third-party call it is in the reference (``cv2.optflow``).
+  TV-L1 solver is by default the third-party call it is in the reference (``cv2.optflow``).
+* ``tvl1_flow``: the native Dual TV-L1 solver (``frlw_tvl1_flow_batch``, csrc/tvl1.hip) on the pairs where they lie in HBM,
+  opt-in through ``generate_opticalflow(..., solver="native")`` / ``-solver native``: its agreement with OpenCV is unmeasured.
 * ``isolated_boxes`` / ``clamp_boxes`` / ``box_flow_density``: per box the mean flow magnitude, the magnitude sum on the GPU
   (``frlw_box_flow_sums``); ``statistics_gt`` / ``statistics_dt`` write the reference's two ``.npz`` files.
 * ``motion_level_map``: five density buckets, the Prophesee box filters, the COCO scorer -> five mAP values.
@@ -33,6 +35,8 @@ FLOW_WINDOW = 500000   # generate_opticalflow.py:106,110
 CUT = 50000            # :79,83
 TOL = 4999             # motion_level_statistics_dt.py:51, motion_level_evaluation.py:22
 FLOW_GROUP_BYTES = 256 << 20   # flows uploaded per box-sum call (a 1280x720 flow is 7 MB)
+TVL1_GROUP_BYTES = 1 << 30     # workspace of one tvl1_flow call (a 1280x720 pair asks for 87 MB, a GEN1 pair for 7 MB)
+SOLVERS = ("cv2", "native")
 
 
 def _shape(dataset):
@@ -119,6 +123,61 @@ def time_surface_pairs(dat, ranges, shape, check=True):
             pairs[i].copy_(torch.from_numpy(time_surface_numpy(host, (H, W))))
             tally["host_windows"] += 1
     return out, tally
+
+
+_TVL1_WORKSPACES = {}
+
+
+def tvl1_counts():
+    """(calls of frlw_tvl1_flow_batch served, kernel launches they enqueued) in this process."""
+    c = (C.c_uint64 * 2)()
+    _lib.check(_lib.load().frlw_tvl1_counts(c), "frlw_tvl1_counts")
+    return int(c[0]), int(c[1])
+
+
+def tvl1_plan(shape, nscales=5, scale_step=0.8):
+    """``frlw_tvl1_plan``: the level shapes of the solver's pyramid, the full frame first; [] = a side below 16."""
+    hw = (C.c_int * (2 * _lib.TVL1_MAX_LEVELS))()
+    n = _lib.load().frlw_tvl1_plan(int(shape[0]), int(shape[1]), int(nscales), float(scale_step), hw)
+    return [(int(hw[2 * i]), int(hw[2 * i + 1])) for i in range(n)]
+
+
+def tvl1_flow(pairs, params=None, return_iters=False):
+    """Dual TV-L1 flow of every pair of ``pairs``, a ``(n, 2, H, W)`` uint8 CUDA tensor as ``time_surface_pairs`` returns it ->
+    ``(n, H, W, 2)`` float32 on the same device, ``[..., 0]`` the x component: what ``box_flow_sums`` reads, no copy in between.
+    ``params``: a dict of ``_lib.FrlwTvl1Params.DEFAULTS`` overrides (OpenCV's defaults when None).  Any ``n``: the pairs go out in
+    groups of at most 64 whose workspace stays under TVL1_GROUP_BYTES.  ``return_iters``: also the ``(n, levels, warps)`` int32
+    tensor of inner iterations run (level 0 = the full frame).  A pair's flow does not depend on its group or its place in it."""
+    if not torch.is_tensor(pairs) or not pairs.is_cuda:
+        raise ValueError("pairs must be a CUDA tensor")
+    if pairs.dtype != torch.uint8 or pairs.dim() != 4 or pairs.shape[1] != 2:
+        raise ValueError("pairs must be a (n, 2, H, W) uint8 tensor")
+    n, H, W = int(pairs.shape[0]), int(pairs.shape[2]), int(pairs.shape[3])
+    if H < 16 or W < 16:
+        raise ValueError(f"a {H} x {W} frame has a side below 16: no pyramid level")
+    prm = _lib.FrlwTvl1Params(**(params or {}))
+    lib = _lib.load()
+    levels = len(tvl1_plan((H, W), prm.nscales, prm.scale_step))
+    one = lib.frlw_tvl1_workspace_bytes(1, H, W, C.byref(prm))
+    if one == 0 or levels == 0:
+        raise ValueError("parameters or shape outside the TV-L1 path")
+    group = _lib.MAX_SEQUENCES
+    while group > 1 and lib.frlw_tvl1_workspace_bytes(group, H, W, C.byref(prm)) > TVL1_GROUP_BYTES:
+        group -= 1
+    p = pairs.contiguous()
+    flows = torch.empty((n, H, W, 2), dtype=torch.float32, device=p.device)
+    iters = torch.empty((n, levels, prm.warps), dtype=torch.int32, device=p.device) if return_iters else None
+    for b0 in range(0, n, group):
+        B = min(group, n - b0)
+        need = lib.frlw_tvl1_workspace_bytes(B, H, W, C.byref(prm))
+        key = (p.device.index, torch.cuda.current_stream().cuda_stream)
+        ws = _TVL1_WORKSPACES.get(key)
+        if ws is None or ws.numel() < need:   # (no encoder header in this workspace: a plain buffer, kept per device and stream)
+            ws = _TVL1_WORKSPACES[key] = torch.empty(need, dtype=torch.uint8, device=p.device)
+        _lib.check(lib.frlw_tvl1_flow_batch(er._ptr(p[b0:b0 + B]), B, H, W, C.byref(prm), er._ptr(flows[b0:b0 + B]),
+                                            er._ptr(iters[b0:b0 + B]) if return_iters else None, er._ptr(ws), ws.numel(), er._stream()),
+                   "frlw_tvl1_flow_batch")
+    return (flows, iters) if return_iters else flows
 
 
 # ------------------------------------------------------------------------------------------------
@@ -375,15 +434,23 @@ def _tvl1():
         return None
 
 
-def generate_opticalflow(raw_dir, dataset="gen1", flow_dir="optical_flow_buffer", surface_dir="time_surface_buffer", device="cuda"):
+def generate_opticalflow(raw_dir, dataset="gen1", flow_dir="optical_flow_buffer", surface_dir="time_surface_buffer", device="cuda",
+                         solver=None):
     """generate_opticalflow.py:94-193: per label of ``<raw_dir>/test`` the time-surface pair of the 500 ms in front of it and the
     TV-L1 flow between the two -> ``<flow_dir>/<file>_<t>.npy``.  A file goes to HBM once and its labels through
-    ``time_surface_pairs``; labels whose output exists are skipped.  Without ``cv2.optflow`` the pairs themselves are saved under
-    ``<surface_dir>/<file>_<t>.npy`` for a machine that has it.  Returns the number of files written."""
+    ``time_surface_pairs``; labels whose output exists are skipped.  ``solver``: None -- ``cv2.optflow`` where it is installed,
+    else the pairs themselves are saved under ``<surface_dir>/<file>_<t>.npy`` for a machine that has it; ``"cv2"`` -- the same
+    solver, its absence an error; ``"native"`` -- ``tvl1_flow`` on the pairs where they lie (cv2 is not imported).  Returns the
+    number of files written."""
     shape = _shape(dataset)
-    create = _tvl1()
-    target = flow_dir if create is not None else surface_dir
-    if create is None:
+    if solver not in (None,) + SOLVERS:
+        raise ValueError(f"solver must be one of {SOLVERS} or None")
+    create = None if solver == "native" else _tvl1()
+    if solver == "cv2" and create is None:
+        raise SystemExit("-solver cv2: cv2.optflow is not installed (-solver native runs the built-in Dual TV-L1)")
+    save_pairs = create is None and solver != "native"
+    target = surface_dir if save_pairs else flow_dir
+    if save_pairs:
         print(f"cv2.optflow is not installed: saving the time-surface pairs under {surface_dir}/ instead of TV-L1 flows")
     os.makedirs(target, exist_ok=True)
     root = os.path.join(raw_dir, "test")
@@ -399,22 +466,29 @@ def generate_opticalflow(raw_dir, dataset="gen1", flow_dir="optical_flow_buffer"
         dat = f_event.to_device(device=device)
         for j0 in range(0, len(jobs), _lib.MAX_SEQUENCES):
             part = jobs[j0:j0 + _lib.MAX_SEQUENCES]
-            pairs = time_surface_pairs(dat, [(lo, hi) for lo, hi, _ in part], shape)[0].cpu().numpy()
-            for pair, (_, _, path) in zip(pairs, part):
-                np.save(path, pair if create is None else create().calc(pair[0], pair[1], None), allow_pickle=True)
+            pairs = time_surface_pairs(dat, [(lo, hi) for lo, hi, _ in part], shape)[0]
+            if solver == "native":
+                out = tvl1_flow(pairs).cpu().numpy()
+            else:
+                pairs = pairs.cpu().numpy()
+                out = pairs if create is None else [create().calc(pair[0], pair[1], None) for pair in pairs]
+            for item, (_, _, path) in zip(out, part):
+                np.save(path, item, allow_pickle=True)
                 n_files += 1
     return n_files
 
 
-def _parser(flags):
+def _parser(flags, solver=False):
     p = argparse.ArgumentParser(description="visualize one or several event files along with their boxes")
     for flag, default in flags:
         p.add_argument(*flag, type=str, **({} if default is None else {"default": default}))
+    if solver:   # not one of the script's own flags: absent = cv2.optflow where installed, else the pairs are saved
+        p.add_argument("-solver", choices=SOLVERS, default=None, help="the TV-L1 solver: OpenCV's, or the built-in one (opt-in)")
     return p
 
 
 PARSERS = {   # the scripts' own flags and defaults
-    "generate_opticalflow": lambda: _parser([(("-raw_dir",), None), (("-dataset", "--dataset"), "gen1")]),
+    "generate_opticalflow": lambda: _parser([(("-raw_dir",), None), (("-dataset", "--dataset"), "gen1")], solver=True),
     "motion_level_statistics_gt": lambda: _parser([(("-raw_dir",), None), (("-dataset", "--dataset"), None)]),
     "motion_level_statistics_dt": lambda: _parser([(("-raw_dir",), None), (("-dataset", "--dataset"), "gen1"), (("-exp_name",), None)]),
     "motion_level_evaluation": lambda: _parser([(("-dataset", "--dataset"), "gen1"), (("-exp_name",), None)]),
@@ -426,7 +500,7 @@ def main(which, argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("the motion-level commands run on the GPU: no ROCm device is visible (there is no CPU fallback)")
     if which == "generate_opticalflow":
-        print(f"{which}: {generate_opticalflow(args.raw_dir, args.dataset)} files written")
+        print(f"{which}: {generate_opticalflow(args.raw_dir, args.dataset, solver=args.solver)} files written")
     elif which == "motion_level_statistics_gt":
         print(f"{which}: {statistics_gt(args.raw_dir, args.dataset)}")
     elif which == "motion_level_statistics_dt":

@@ -370,6 +370,56 @@ int frlw_box_flow_sums(const float *flows, int n_flows, int H, int W, const int3
  * frlw_box_flow_sums (host-side: ENQUEUES). */
 int frlw_motion_counts(uint64_t counts[2]);
 
+/*
+ * Dual TV-L1 optical flow (Zach, Pock, Bischof 2007) between the two images of n_pairs <= FRLW_MAX_SEQUENCES uint8 pairs in one
+ * launch sequence (csrc/tvl1.hip) -- the solver generate_opticalflow.py:189-190 calls, with its default parameters, as DESIGN.md's
+ * motion section specifies it and tests/tvl1_restated.py restates it.  float32 throughout; no illumination term, no initial flow.
+ *
+ * frlw_tvl1_params_t: `struct_size` = sizeof(frlw_tvl1_params_t) as the CALLER compiled it, read like frlw_tuning_t's (fields
+ * outside it take their defaults; below 8 or above 4096 is FRLW_ERR_ARG).  NULL = every default.  nscales 1..FRLW_TVL1_MAX_LEVELS,
+ * warps 1..64, inner and outer >= 1, median 5 (the 5 x 5 median of the flow in front of every outer iteration) or <= 1 (none),
+ * tau, lambda, theta > 0, epsilon >= 0 (0: every loop runs its full count), scale_step in [0.25, 0.95]; else FRLW_ERR_ARG.
+ *
+ * frlw_tvl1_plan (HOST only): the pyramid of an H x W frame -- level 0 the frame, level s the bilinear resize of level s - 1 to
+ * (round(h * scale_step), round(w * scale_step)), the first level with a side below 16 dropped with all above it.  Returns the
+ * number of levels (0: the frame itself has a side below 16, or a bad argument) and writes h, w of each to levels_hw (2 ints per
+ * level, room for FRLW_TVL1_MAX_LEVELS; may be NULL).
+ *
+ * frlw_tvl1_workspace_bytes (HOST only, 64-bit arithmetic: 64 pairs of 1280 x 720 ask for more than 4 GB): about 94 bytes per
+ * pixel and pair; 0 = n_pairs outside 1..FRLW_MAX_SEQUENCES, a frame with a side below 16 or above 16384, or bad parameters.
+ *
+ * frlw_tvl1_flow_batch: pairs DEVICE (n_pairs, 2, H, W) uint8 -- what frlw_time_surface_batch writes; flows DEVICE (n_pairs, H,
+ * W, 2) float32, 8-byte aligned, [..., 0] the x and [..., 1] the y component -- what frlw_box_flow_sums reads; iters_out DEVICE
+ * (n_pairs, levels, warps) int32 or NULL: the inner iterations each pair ran per level (0 = the full frame) and warp; workspace
+ * 16-byte aligned.  Pairs run through levels and warps in lockstep, each with its own error, "done" word and counters on the
+ * device; a pair that has converged costs its workgroups one read.  The flow of a pair is bit-identical from run to run and
+ * whether it is encoded alone or at any place of a batch.  NOT capturable: once per outer iteration the host reads the pairs'
+ * done words (n_pairs ints, one stream synchronisation) to stop enqueuing when every pair is through with the warp.  Plain
+ * launches only: no workgroup waits on another.  Bad arguments: FRLW_ERR_ARG, nothing enqueued; FRLW_ERR_WORKSPACE likewise.
+ */
+#define FRLW_TVL1_MAX_LEVELS 8
+typedef struct frlw_tvl1_params {
+    int32_t struct_size; /* = sizeof(frlw_tvl1_params_t) */
+    int32_t nscales;     /* 5 */
+    int32_t warps;       /* 5 */
+    int32_t inner;       /* 30 */
+    int32_t outer;       /* 10 */
+    int32_t median;      /* 5 */
+    float tau;           /* 0.25 */
+    float lambda;        /* 0.15 */
+    float theta;         /* 0.3 */
+    float epsilon;       /* 0.01 */
+    float scale_step;    /* 0.8 */
+} frlw_tvl1_params_t;
+int frlw_tvl1_plan(int H, int W, int nscales, double scale_step, int *levels_hw);
+size_t frlw_tvl1_workspace_bytes(int n_pairs, int H, int W, const frlw_tvl1_params_t *params);
+int frlw_tvl1_flow_batch(const uint8_t *pairs, int n_pairs, int H, int W, const frlw_tvl1_params_t *params, float *flows,
+                         int32_t *iters_out, void *workspace, size_t workspace_bytes, frlw_stream_t stream);
+
+/* The solver's own counters (frlw_motion_counts keeps its two slots): counts[0] = calls of frlw_tvl1_flow_batch served, counts[1] =
+ * kernel launches they enqueued (host-side: ENQUEUES). */
+int frlw_tvl1_counts(uint64_t counts[2]);
+
 /* The verdict of the one-time LDS lane-order self-test of the fast paths (frlw_taf_encode_batch, frlw_ev_encode_batch, the
  * two-launch forms of frlw_sae_encode / frlw_eci_encode) for the CURRENT device: *ok_out = 1 when the property held, 0 when
  * it did not (those entry points then answer FRLW_ERR_UNSUPPORTED and callers take the general path -- same bits, different
