@@ -404,6 +404,61 @@ def test_baseconv_train_forms(case, mode):
         judge(dw, wgrad_ref(x, dz, w.shape, s), wgrad_ref(x.abs(), dz.abs(), w.shape, s), "randn", prec, f"{name} {pname} dw")
 
 
+PAIR = [  # (name, H, W, stride, precisions); the parity-grouped operand in the bf16x3 arithmetic needs Cout % 16 == 0
+    ("stride 1", 8, 8, 1, ("f32", "bf16x3")),
+    ("stride 2, transposed gather", 9, 9, 2, ("f32", "bf16x3")),
+    ("stride 2, parity classes", 8, 8, 2, ("f32",)),
+]
+
+
+@pytest.mark.parametrize("case", PAIR, ids=_ids(PAIR))
+def test_baseconv_train_stacked_pair_without_operand_cache(case):
+    """Two blocks stacked along the output channels (frlw_baseconv_fuse_t::split) with no w_cache in either direction: the forward
+    lays the stacked forward operand out in its scratch, the backward the stacked data-gradient operand (k_weight_layouts reading
+    two weights, parity-grouped in the third case).  z, dx and dw by (b) against float64 on the concatenated weight, BatchNorm +
+    SiLU per channel on the concatenated rows."""
+    import test_bn_silu_forms_gpu as bnf
+    L, lib = _lib()
+    name, H, W, s, precs = case
+    B, Cin, c1, Cout, k = 2, 8, 16, 36, 3
+    Ho, Wo = (H + 2 - k) // s + 1, (W + 2 - k) // s + 1
+    g = torch.Generator(device="cuda").manual_seed(seed(name, "pair"))
+    x, w = gen((B, H, W, Cin), "randn", g), gen((Cout, Cin, k, k), "randn", g)
+    gamma = torch.rand(Cout, generator=g, device="cuda") + 0.5
+    beta = torch.randn(Cout, generator=g, device="cuda") * 0.2
+    dy = torch.randn(B, Ho, Wo, Cout, generator=g, device="cuda")
+    first = [t[:c1].contiguous() for t in (w, gamma, beta)]
+    second = [t[c1:].contiguous() for t in (w, gamma, beta)]
+    dy1, dy2 = dy[..., :c1].contiguous(), dy[..., c1:].contiguous()
+    ref, absref = conv_ref(x, w, s), conv_ref(x.abs(), w.abs(), s)
+    nbytes = lib.frlw_baseconv_train_scratch_bytes(B, H, W, Cin, Cout, k, s)
+    cnt = torch.zeros(1024, dtype=torch.int32, device="cuda")
+    for pname in precs:
+        prec = PREC[pname]
+        nan = lambda *sh: torch.full(sh, float("nan"), device="cuda")
+        scratch = torch.full((nbytes,), 0xFF, dtype=torch.uint8, device="cuda")  # NaN wherever a float is read unwritten
+        z, y1, y2 = nan(B, Ho, Wo, Cout), nan(B, Ho, Wo, c1), nan(B, Ho, Wo, Cout - c1)
+        mean, var, invstd = nan(Cout), nan(Cout), nan(Cout)
+        fuse = L.FrlwBaseconvFuse(split=c1, w2=second[0].data_ptr(), gamma2=second[1].data_ptr(), beta2=second[2].data_ptr(),
+                                  y2=y2.data_ptr(), dy2=dy2.data_ptr())
+        check_rc(lib.frlw_baseconv_train_fwd(ptr(x), ptr(first[0]), ptr(first[1]), ptr(first[2]), C.c_float(1e-5), B, H, W, Cin, Cout, k, s,
+                                             ptr(z), ptr(y1), ptr(mean), ptr(var), ptr(invstd), None, None, C.c_float(0.1), None,
+                                             None, ptr(scratch), nbytes, ptr(cnt), C.byref(fuse), prec, None), "train_fwd")
+        judge(z, ref, absref, "randn", prec, f"{name} {pname} z")
+        dz, dx, dw = nan(B, Ho, Wo, Cout), nan(B, H, W, Cin), nan(Cout, Cin, k, k)
+        dgamma, dbeta = nan(Cout), nan(Cout)
+        check_rc(lib.frlw_baseconv_train_bwd(ptr(dy1), 0, ptr(x), ptr(z), ptr(first[0]), ptr(first[1]), ptr(first[2]), ptr(mean), ptr(invstd),
+                                             B, H, W, Cin, Cout, k, s, ptr(dz), ptr(dx), ptr(dw), ptr(dgamma), ptr(dbeta), None,
+                                             ptr(scratch), nbytes, ptr(cnt), C.byref(fuse), prec, None), "train_bwd")
+        torch.cuda.synchronize()
+        assert int(cnt.abs().sum()) == 0, "arrival counters not reset"
+        bn_ref = bnf.reference(z.reshape(-1, Cout), gamma, beta, dy.reshape(-1, Cout))
+        bnf.assert_ok(bnf.judge(bn_ref, dict(mean=mean, var=var, invstd=invstd, y=torch.cat([y1, y2], -1).reshape(-1, Cout),
+                                             dz=dz.reshape(-1, Cout), dgamma=dgamma, dbeta=dbeta)), f"{name} {pname} BatchNorm + SiLU")
+        judge(dx, dgrad_ref(dz, w, s, H, W), dgrad_ref(dz.abs(), w.abs(), s, H, W), "randn", prec, f"{name} {pname} dx")
+        judge(dw, wgrad_ref(x, dz, w.shape, s), wgrad_ref(x.abs(), dz.abs(), w.shape, s), "randn", prec, f"{name} {pname} dw")
+
+
 # ---- detector plans --------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("mode", ["int", "randn"])

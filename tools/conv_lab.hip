@@ -1,5 +1,5 @@
 // conv_lab.hip -- stand-alone timing harness for the fp32-MFMA convolution kernel (csrc/conv_mfma.h).
-//   hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -I frlw-evd_amd/csrc tools/conv_lab.hip -o build/conv_lab
+//   hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -I include -I frlw-evd_amd/csrc tools/conv_lab.hip -o build/conv_lab
 //   build/conv_lab [B]          prints per-shape time / TFLOP/s and the workgroups-per-CU spread of the launch
 // Developer tool: nothing imports it.  It runs the kernels that ship (launch_conv); the numeric thresholds of the tile choice can
 // be moved through the environment (dev_knob of conv_mfma.h), -DCONV_LAB_PROBE adds the per-workgroup timeline probe.
@@ -8,7 +8,9 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <atomic>
 #include <vector>
+#include "frlw_evd.h"
 #define FRLW_DEV_BUILD 1
 namespace {
 #include "conv_mfma.h"

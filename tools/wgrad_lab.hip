@@ -1,5 +1,5 @@
 // wgrad_lab.hip -- stand-alone timing harness for the fp32-MFMA weight-gradient kernel (csrc/wgrad_mfma.h).
-//   hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -I frlw-evd_amd/csrc tools/wgrad_lab.hip -o build/wgrad_lab
+//   hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -I include -I frlw-evd_amd/csrc tools/wgrad_lab.hip -o build/wgrad_lab
 //   build/wgrad_lab [B] [reps] [first n shapes]     per-shape time / TFLOP/s and a checksum of the partial tiles' sum
 // Developer tool: nothing imports it.
 #include <hip/hip_runtime.h>
@@ -7,7 +7,9 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <atomic>
 #include <vector>
+#include "frlw_evd.h"
 #define FRLW_DEV_BUILD 1
 namespace {
 #include "conv_mfma.h"
