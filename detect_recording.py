@@ -28,8 +28,19 @@ def build_parser():
     parser.add_argument("--frames_per_call", type=int, default=32)
     parser.add_argument("--t_begin", type=int, default=0)
     parser.add_argument("--t_end", type=int, default=None)            # default: the last event
+    parser.add_argument("--seq_nms", choices=("off", "stop", "skip"), default="off")   # Seq-NMS over the whole recording
+    parser.add_argument("--seq_nms_metric", choices=("avg", "max"), default="avg")
+    parser.add_argument("--seq_nms_drop", action="store_true")        # remove the boxes a sequence suppresses
     parser.set_defaults(record=None, bbox_path=None, data_path=None, batch_size=1, num_cpu_workers=1, nodes=1, metric="none")
     return parser
+
+
+def seq_nms_options(args):
+    """``StreamDetector``'s ``seq_nms`` argument for the flags: None when off; ``stop`` ends where the reference ends (a single box
+    outranks every remaining sequence), ``skip`` goes on until no sequence of two boxes is left."""
+    if args.seq_nms == "off":
+        return None
+    return {"isolated": args.seq_nms, "metric": args.seq_nms_metric, "drop_suppressed": bool(args.seq_nms_drop)}
 
 
 def build_model(args):
@@ -62,13 +73,14 @@ def main(argv=None):
     sensor, _ = SHAPES["gen4" if args.dataset == "gen4" else "gen1"]
     f_event = dat_io.DatFile(args.dat)
     det = StreamDetector(net, sensor, settings.img_size, dataset=args.dataset, volume_bins=8, input_bins=args.event_volume_bins,
-                         period_us=args.period, frames_per_call=args.frames_per_call)
+                         period_us=args.period, frames_per_call=args.frames_per_call, seq_nms=seq_nms_options(args))
     t_end = f_event.total_time() if args.t_end is None else args.t_end
     boxes = det.run(f_event.to_device(device=settings.gpu_device), args.t_begin, t_end)
     path = args.out if args.out.endswith(".npy") else args.out + ".npy"
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     np.save(path, boxes)
-    print({"frames": len(det.frame_times(args.t_begin, t_end)), "boxes": int(len(boxes)), "out": path})
+    print({"frames": len(det.frame_times(args.t_begin, t_end)), "boxes": int(len(boxes)), "sequences": int(det.sequences),
+           "out": path})
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
     return boxes

@@ -21,6 +21,9 @@ FRLW_ERR_SPAN = -7
 MAX_SEQUENCES = 64
 MAX_LAMDAS = 8
 TVL1_MAX_LEVELS = 8
+SEQ_NMS_MAX_FRAMES = 4096
+SEQ_NMS_MAX_BOXES = 64
+SEQ_NMS_TRUNCATED = 1   # status bit: the selection loop ended at max_sequences
 
 # the FRLW_CONV_PATH_* counters of frlw_conv_path_counts, in the header's enum order (lower case, prefix dropped)
 CONV_PATHS = ("128x32", "128x128_4x1", "128x128_2x2", "64x128", "64x64", "split_vec", "split_scalar", "split_inkernel",
@@ -156,6 +159,9 @@ SYMBOLS = {
     "frlw_tvl1_workspace_bytes": (_SZ, [_I, _I, _I, _P]),
     "frlw_tvl1_flow_batch": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _SZ, _P]),
     "frlw_tvl1_counts": (_I, [C.POINTER(C.c_uint64)]),
+    "frlw_seq_nms_workspace_bytes": (_SZ, [_I64, _I64, _I]),
+    "frlw_seq_nms": (_I, [_P, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, C.c_double, C.c_double, _I, _I, _I, _P, _P, _P, _P,
+                         _P, _SZ, _P]),
     "frlw_leaky_transform": (_I, [_P, _I64, _P, _P, _P]),
     "frlw_resize_nearest_f32": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "frlw_resize_nearest_u8": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),

@@ -27,10 +27,12 @@ class StreamDetector:
     (``generate_taf.py``: 8); ``input_bins``: what the dataset class would read for ``--event_volume_bins`` -- K (the ``bins{K/2}``
     file followed by the ``bins{K}`` file: all 2K channels, newest slot first) or K / 2 (the ``bins{K/2}`` file alone: the newest
     K / 2 slots).  A frame every ``period_us``, a multiple of the FIFO window ``window_us``; ``frames_per_call`` frames (at most
-    64) per encode call and per detector batch."""
+    64) per encode call and per detector batch.  ``seq_nms``: None, or a dict of ``seq_nms.rescore_frames`` arguments (``isolated``,
+    ``metric``, ``drop_suppressed``, thresholds): ``run`` then links the boxes of the whole recording, writes the rescored
+    confidences and the sequence ids (``track_id``) and leaves the number of sequences in ``self.sequences``."""
 
     def __init__(self, model, sensor_shape, img_size, dataset="gen1", volume_bins=8, input_bins=8, period_us=50000,
-                 window_us=10000, frames_per_call=32):
+                 window_us=10000, frames_per_call=32, seq_nms=None):
         self.model = model
         self.sensor_shape = (int(sensor_shape[0]), int(sensor_shape[1]))
         self.img_size = (int(img_size[0]), int(img_size[1]))
@@ -48,6 +50,8 @@ class StreamDetector:
         if not 1 <= self.frames_per_call <= er._lib.MAX_SEQUENCES:
             raise ValueError(f"frames_per_call: 1..{er._lib.MAX_SEQUENCES}")
         self.dataset = dataset
+        self.seq_nms = None if seq_nms is None else dict(seq_nms)
+        self.sequences = 0
         self.evaluator = evaluator(None, self.frames_per_call, 10000, self.sensor_shape[1], self.sensor_shape[0], self.img_size[1],
                                    self.img_size[0], dataset)
 
@@ -85,7 +89,7 @@ class StreamDetector:
         """``dat``: the time-sorted raw records of the recording on the GPU (``DatFile.to_device()``).  The FIFO state starts at
         -6000 at ``t_begin``; frame ``j`` holds the events with ``t_begin <= t < t_begin + j * period_us`` (an event on a frame
         boundary belongs to the later frame).  Returns the boxes of all frames as one structured array with the fields of a
-        ``*_bbox.npy`` file (``track_id`` 0), in frame order."""
+        ``*_bbox.npy`` file (``track_id`` 0 unless ``seq_nms`` is set), in frame order."""
         rows = dat.contiguous().view(torch.uint8).reshape(-1, 8)
         device = rows.device
         enc, xmap, ymap = self.geometry(device)
@@ -105,6 +109,9 @@ class StreamDetector:
                 with torch.no_grad():
                     outputs = self.model.detect(self.hand_off(u8, enc))
                 out += self.boxes(outputs, stamps)
+        if self.seq_nms is not None:
+            from .seq_nms import rescore_frames
+            out, self.sequences = rescore_frames(out, **self.seq_nms)
         return to_bbox_records(out, times)
 
 

@@ -420,6 +420,39 @@ int frlw_tvl1_flow_batch(const uint8_t *pairs, int n_pairs, int H, int W, const 
  * kernel launches they enqueued (host-side: ENQUEUES). */
 int frlw_tvl1_counts(uint64_t counts[2]);
 
+/*
+ * Seq-NMS over the detections of n_videos <= FRLW_MAX_SEQUENCES recordings in one call (csrc/seq_nms.hip) -- what the reference's
+ * core/Others/seqnms/seq_nms.py computes, as DESIGN.md's Seq-NMS section specifies it and tests/seqnms_restated.py restates it.
+ * Recording v is the frames [video_frame_start[v], video_frame_start[v + 1]), at most FRLW_SEQ_NMS_MAX_FRAMES of them; frame f is the
+ * boxes [frame_start[f], frame_start[f + 1]), at most FRLW_SEQ_NMS_MAX_BOXES.  Both offset arrays are HOST arrays (n_videos + 1 and
+ * n_frames_total + 1 entries, starting at 0, ascending): every limit is checked on them before anything is enqueued, and they
+ * are copied into the workspace.  boxes DEVICE (total, 4) float32 x1, y1, x2, y2, 16-byte aligned; scores DEVICE float64, >= 0;
+ * labels DEVICE int32.
+ *
+ * Box i of frame f links to box j of frame f + 1 when the labels are equal and IoU >= link_thr (float64, areas without + 1).
+ * Then, again and again: the path with the largest sum of scores (ties: the lowest start frame, the lowest box; inside a path
+ * the lowest successor) is selected, its boxes are rescored (metric 0: sum / length, 1: the largest member) and every box of
+ * a path frame with IoU >= nms_thr against the path's box -- any label, the path's box included -- loses all its edges.
+ * isolated 0: the loop ends when the best path is a single box (the reference's rule); 1: single boxes are no candidates, the
+ * loop ends when no path of two or more boxes is left.  max_sequences >= 1 bounds the loop: reaching it ends it and sets
+ * FRLW_SEQ_NMS_TRUNCATED in status[v]; the outputs then hold the sequences selected so far.  nms_thr <= 1 (else FRLW_ERR_ARG):
+ * a path's own boxes then always leave the graph, so the loop ends after at most total / 2 rounds whatever max_sequences says.
+ *
+ * Outputs, DEVICE, per box: out_scores float64 (the rescored score, else the input), out_seq int32 (1-based order of selection
+ * inside the recording, 0: on no sequence), out_flags uint8 (bit 0: suppressed by a sequence it is not on); status DEVICE int32
+ * per recording.  Two launches, no host synchronisation, one wavefront per recording in the second: no workgroup waits on another.
+ * frlw_seq_nms_workspace_bytes is HOST only (25 bytes per box and the offsets); 0 = arguments over the limits.  Null pointers
+ * or offsets over the limits: FRLW_ERR_ARG; a short workspace: FRLW_ERR_WORKSPACE; nothing is enqueued in either case.
+ */
+#define FRLW_SEQ_NMS_MAX_FRAMES 4096
+#define FRLW_SEQ_NMS_MAX_BOXES 64
+#define FRLW_SEQ_NMS_TRUNCATED 1
+size_t frlw_seq_nms_workspace_bytes(int64_t total_boxes, int64_t n_frames_total, int n_videos);
+int frlw_seq_nms(const float *boxes, const double *scores, const int32_t *labels, const int32_t *frame_start,
+                 const int32_t *video_frame_start, int n_videos, double link_thr, double nms_thr, int metric, int isolated,
+                 int max_sequences, double *out_scores, int32_t *out_seq, uint8_t *out_flags, int32_t *status, void *workspace,
+                 size_t workspace_bytes, frlw_stream_t stream);
+
 /* The verdict of the one-time LDS lane-order self-test of the fast paths (frlw_taf_encode_batch, frlw_ev_encode_batch, the
  * two-launch forms of frlw_sae_encode / frlw_eci_encode) for the CURRENT device: *ok_out = 1 when the property held, 0 when
  * it did not (those entry points then answer FRLW_ERR_UNSUPPORTED and callers take the general path -- same bits, different
