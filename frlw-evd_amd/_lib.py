@@ -216,7 +216,9 @@ SYMBOLS = {
                                     _P, _I64, _P, _P, _I, _P]),
     "frlw_spp_train_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "frlw_spp_train_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "frlw_spp_train_plan": (_I, [_I, _I, _I, _I, C.POINTER(C.c_int32)]),
     "frlw_pred_bwd_scratch_floats": (_I64, [_I64, _I, _I]),
+    "frlw_pred_plan": (_I, [_I64, _I, _I, C.POINTER(C.c_int32)]),
     "frlw_pred_fwd": (_I, [_P, _P, _I64, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "frlw_pred_bwd": (_I, [_P, _P, _P, _I64, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "frlw_simota_workspace_bytes": (_SZ, [_I, _I, _I]),

@@ -278,14 +278,51 @@ inline int pred_waves(long long M)
     return (int)wg * kPredWaves;
 }
 
+// [workgroup][5 + nc][C] weight-gradient partials, then [workgroup][16] bias partials (PredArgs::partial)
+inline int64_t pred_scratch_floats(int n_wg, int C, int nc) { return (int64_t)n_wg * (5 + nc) * C + (int64_t)n_wg * 16; }
+
+// The form of one call: the template arguments of k_pred_fwd / k_pred_bwd and the workgroups of the launch.  The launchers and
+// frlw_pred_plan both take them from here.
+struct PredPlan {
+    int cpl, ng, n_wg;
+};
+
+inline int pred_plan(long long M, int C, int nc, PredPlan &p)
+{
+    if (M < 1) return FRLW_ERR_ARG;
+    if (C < 4 || (C & 3) || C > 512 || nc < 1 || nc > 11) return FRLW_ERR_UNSUPPORTED;
+    p.cpl = C > 256 ? 2 : 1;
+    p.ng = 5 + nc > 8 ? 2 : 1;
+    p.n_wg = pred_waves(M) / kPredWaves;
+    return FRLW_OK;
+}
+
+typedef void (*PredKernel)(PredArgs);
+inline PredKernel pred_fwd_kernel(const PredPlan &p)
+{
+    return p.ng == 1 ? (p.cpl == 1 ? k_pred_fwd<1, 1> : k_pred_fwd<2, 1>) : (p.cpl == 1 ? k_pred_fwd<1, 2> : k_pred_fwd<2, 2>);
+}
+inline PredKernel pred_bwd_kernel(const PredPlan &p)
+{
+    return p.ng == 1 ? (p.cpl == 1 ? k_pred_bwd<1, 1> : k_pred_bwd<2, 1>) : (p.cpl == 1 ? k_pred_bwd<1, 2> : k_pred_bwd<2, 2>);
+}
+
 } // namespace
 
 extern "C" {
 
 int64_t frlw_pred_bwd_scratch_floats(int64_t M, int C, int nc)
 {
-    const int n_wg = pred_waves(M) / kPredWaves;
-    return (int64_t)n_wg * (5 + nc) * C + (int64_t)n_wg * 16;
+    return pred_scratch_floats(pred_waves(M) / kPredWaves, C, nc);
+}
+
+int frlw_pred_plan(int64_t M, int C, int nc, int32_t out[3])
+{
+    if (!out) return FRLW_ERR_ARG;
+    PredPlan p;
+    if (const int rc = pred_plan(M, C, nc, p)) return rc;
+    out[0] = p.cpl; out[1] = p.ng; out[2] = p.n_wg;
+    return FRLW_OK;
 }
 
 int frlw_pred_fwd(const float *reg_feat, const float *cls_feat, int64_t M, int C, int nc, const float *w_reg,
@@ -293,19 +330,14 @@ int frlw_pred_fwd(const float *reg_feat, const float *cls_feat, int64_t M, int C
                   float *out, frlw_stream_t stream)
 {
     (void)hipGetLastError();
-    if (!reg_feat || !cls_feat || !w_reg || !b_reg || !w_obj || !b_obj || !w_cls || !b_cls || !out || M < 1) return FRLW_ERR_ARG;
-    if (C < 4 || (C & 3) || C > 512 || nc < 1 || nc > 11) return FRLW_ERR_UNSUPPORTED;
+    if (!reg_feat || !cls_feat || !w_reg || !b_reg || !w_obj || !b_obj || !w_cls || !b_cls || !out) return FRLW_ERR_ARG;
+    PredPlan p;
+    if (const int rc = pred_plan(M, C, nc, p)) return rc;
     PredArgs a = {};
     a.reg_feat = reg_feat; a.cls_feat = cls_feat; a.w_reg = w_reg; a.w_obj = w_obj; a.w_cls = w_cls;
     a.b_reg = b_reg; a.b_obj = b_obj; a.b_cls = b_cls; a.M = M; a.C = C; a.nc = nc; a.out = out;
-    a.n_waves = pred_waves(M);
-    const dim3 grid(a.n_waves / kPredWaves), block(64 * kPredWaves);
-    hipStream_t s = (hipStream_t)stream;
-    const bool two_c = C > 256, two_g = 5 + nc > 8;
-    if (!two_c && !two_g) hipLaunchKernelGGL((k_pred_fwd<1, 1>), grid, block, 0, s, a);
-    else if (two_c && !two_g) hipLaunchKernelGGL((k_pred_fwd<2, 1>), grid, block, 0, s, a);
-    else if (!two_c) hipLaunchKernelGGL((k_pred_fwd<1, 2>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_pred_fwd<2, 2>), grid, block, 0, s, a);
+    a.n_waves = p.n_wg * kPredWaves;
+    hipLaunchKernelGGL(pred_fwd_kernel(p), dim3(p.n_wg), dim3(64 * kPredWaves), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? FRLW_OK : FRLW_ERR_HIP;
 }
 
@@ -316,24 +348,20 @@ int frlw_pred_bwd(const float *reg_feat, const float *cls_feat, const float *dou
 {
     (void)hipGetLastError();
     if (!reg_feat || !cls_feat || !dout || !w_reg || !w_obj || !w_cls || !d_reg_feat || !d_cls_feat || !dw_reg || !db_reg ||
-        !dw_obj || !db_obj || !dw_cls || !db_cls || !scratch || M < 1)
+        !dw_obj || !db_obj || !dw_cls || !db_cls || !scratch)
         return FRLW_ERR_ARG;
-    if (C < 4 || (C & 3) || C > 512 || nc < 1 || nc > 11) return FRLW_ERR_UNSUPPORTED;
-    if (scratch_floats < frlw_pred_bwd_scratch_floats(M, C, nc)) return FRLW_ERR_WORKSPACE;
+    PredPlan p;
+    if (const int rc = pred_plan(M, C, nc, p)) return rc;
+    if (scratch_floats < pred_scratch_floats(p.n_wg, C, nc)) return FRLW_ERR_WORKSPACE;
     PredArgs a = {};
     a.reg_feat = reg_feat; a.cls_feat = cls_feat; a.w_reg = w_reg; a.w_obj = w_obj; a.w_cls = w_cls;
     a.M = M; a.C = C; a.nc = nc; a.dout = dout; a.d_reg = d_reg_feat; a.d_cls = d_cls_feat; a.partial = scratch;
-    a.n_waves = pred_waves(M);
-    const dim3 grid(a.n_waves / kPredWaves), block(64 * kPredWaves);
+    a.n_waves = p.n_wg * kPredWaves;
     hipStream_t s = (hipStream_t)stream;
-    const bool two_c = C > 256, two_g = 5 + nc > 8;
-    if (!two_c && !two_g) hipLaunchKernelGGL((k_pred_bwd<1, 1>), grid, block, 0, s, a);
-    else if (two_c && !two_g) hipLaunchKernelGGL((k_pred_bwd<2, 1>), grid, block, 0, s, a);
-    else if (!two_c) hipLaunchKernelGGL((k_pred_bwd<1, 2>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_pred_bwd<2, 2>), grid, block, 0, s, a);
+    hipLaunchKernelGGL(pred_bwd_kernel(p), dim3(p.n_wg), dim3(64 * kPredWaves), 0, s, a);
     const int nout = 5 + nc, total = nout * C + nout;
-    hipLaunchKernelGGL(k_pred_bwd_final, dim3((total + 15) / 16), dim3(256), 0, s, scratch, a.n_waves / kPredWaves, nout, C, dw_reg, dw_obj,
-                       dw_cls, db_reg, db_obj, db_cls);
+    hipLaunchKernelGGL(k_pred_bwd_final, dim3((total + 15) / 16), dim3(256), 0, s, scratch, p.n_wg, nout, C, dw_reg, dw_obj, dw_cls, db_reg,
+                       db_obj, db_cls);
     return hipGetLastError() == hipSuccess ? FRLW_OK : FRLW_ERR_HIP;
 }
 
@@ -347,6 +375,8 @@ int frlw_pred_bwd(const float *reg_feat, const float *cls_feat, const float *dou
 // pixel looks at the outputs whose window holds it, k = 5, 9, 13, row-major) -- a fixed summation order, no float atomics.
 namespace {
 
+constexpr size_t kSppMaxLds = 144 * 1024; // dynamic LDS bytes a workgroup may ask for (H * W <= 512 at 16 channels)
+
 // channels per workgroup: the widest of 64 / 32 / 16 whose maps (backward: 3 x (float + uint16) per element) fit the LDS AND
 // that still gives the chip 1024 workgroups; otherwise the narrowest that fits.  (The window scans are chains of dependent
 // LDS reads: with 64 channels the 8 x 10 x 256 maps of a batch of 64 were 256 workgroups = one wavefront per SIMD, 290 us.)
@@ -354,11 +384,30 @@ inline int spp_train_ch(int HW, int per_elem_bytes, int C, int B)
 {
     int fit = 0;
     for (int ch = 64; ch >= 16; ch >>= 1) {
-        if ((size_t)HW * ch * per_elem_bytes > 144 * 1024) continue;
+        if ((size_t)HW * ch * per_elem_bytes > kSppMaxLds) continue;
         fit = ch;
         if ((long long)((C + ch - 1) / ch) * B >= 1024) return ch;
     }
     return fit;
+}
+
+// The form of one call, forward and backward alike (the backward needs the most LDS, so it sets the chunking of both).  The
+// launchers and frlw_spp_train_plan both take it from here.
+struct SppPlan {
+    int ch, groups; // channels per workgroup, workgroups per image
+    size_t lds_fwd, lds_bwd;
+};
+
+inline int spp_train_plan(int B, int H, int W, int C, SppPlan &p)
+{
+    if (B < 1 || H < 1 || W < 1 || C < 1) return FRLW_ERR_ARG;
+    if ((long long)H * W > 65535) return FRLW_ERR_UNSUPPORTED; // uint16 arg-max pixels
+    p.ch = spp_train_ch(H * W, 3 * 6, C, B);
+    if (p.ch == 0) return FRLW_ERR_UNSUPPORTED;
+    p.groups = (C + p.ch - 1) / p.ch;
+    p.lds_fwd = (size_t)H * W * p.ch * sizeof(float);
+    p.lds_bwd = (size_t)3 * H * W * p.ch * (sizeof(float) + sizeof(uint16_t));
+    return FRLW_OK;
 }
 
 __global__ __launch_bounds__(256) void k_spp_train_fwd(const float *x, int H, int W, int C, int ch, float *out, uint16_t *arg)
@@ -426,27 +475,36 @@ __global__ __launch_bounds__(256) void k_spp_train_bwd(const float *g, const uin
 
 extern "C" {
 
+int frlw_spp_train_plan(int B, int H, int W, int C, int32_t out[3])
+{
+    if (!out) return FRLW_ERR_ARG;
+    SppPlan p;
+    if (const int rc = spp_train_plan(B, H, W, C, p)) return rc;
+    out[0] = p.ch; out[1] = (int32_t)p.lds_fwd; out[2] = (int32_t)p.lds_bwd;
+    return FRLW_OK;
+}
+
 int frlw_spp_train_fwd(const float *x, int B, int H, int W, int C, float *out, uint16_t *argmax, frlw_stream_t stream)
 {
     (void)hipGetLastError();
-    if (!x || !out || !argmax || B < 1 || H < 1 || W < 1 || C < 1) return FRLW_ERR_ARG;
-    const int ch = spp_train_ch(H * W, 3 * 6, C, B); // the same chunking as the backward, which needs the most LDS
-    if (H * W > 65535 || ch == 0) return FRLW_ERR_UNSUPPORTED;
-    const size_t lds = (size_t)H * W * ch * sizeof(float);
+    if (!x || !out || !argmax) return FRLW_ERR_ARG;
+    SppPlan p;
+    if (const int rc = spp_train_plan(B, H, W, C, p)) return rc;
+    const size_t lds = p.lds_fwd;
     if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)k_spp_train_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k_spp_train_fwd, dim3((C + ch - 1) / ch, B), dim3(256), lds, (hipStream_t)stream, x, H, W, C, ch, out, argmax);
+    hipLaunchKernelGGL(k_spp_train_fwd, dim3(p.groups, B), dim3(256), lds, (hipStream_t)stream, x, H, W, C, p.ch, out, argmax);
     return hipGetLastError() == hipSuccess ? FRLW_OK : FRLW_ERR_HIP;
 }
 
 int frlw_spp_train_bwd(const float *dout, const uint16_t *argmax, int B, int H, int W, int C, float *dx, frlw_stream_t stream)
 {
     (void)hipGetLastError();
-    if (!dout || !argmax || !dx || B < 1 || H < 1 || W < 1 || C < 1) return FRLW_ERR_ARG;
-    const int ch = spp_train_ch(H * W, 3 * 6, C, B);
-    if (H * W > 65535 || ch == 0) return FRLW_ERR_UNSUPPORTED;
-    const size_t lds = (size_t)3 * H * W * ch * (sizeof(float) + sizeof(uint16_t));
+    if (!dout || !argmax || !dx) return FRLW_ERR_ARG;
+    SppPlan p;
+    if (const int rc = spp_train_plan(B, H, W, C, p)) return rc;
+    const size_t lds = p.lds_bwd;
     if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)k_spp_train_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k_spp_train_bwd, dim3((C + ch - 1) / ch, B), dim3(256), lds, (hipStream_t)stream, dout, argmax, H, W, C, ch, dx);
+    hipLaunchKernelGGL(k_spp_train_bwd, dim3(p.groups, B), dim3(256), lds, (hipStream_t)stream, dout, argmax, H, W, C, p.ch, dx);
     return hipGetLastError() == hipSuccess ? FRLW_OK : FRLW_ERR_HIP;
 }
 

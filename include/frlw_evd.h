@@ -632,6 +632,11 @@ int frlw_pred_bwd(const float *reg_feat, const float *cls_feat, const float *dou
                   const float *w_reg, const float *w_obj, const float *w_cls, float *d_reg_feat, float *d_cls_feat,
                   float *dw_reg, float *db_reg, float *dw_obj, float *db_obj, float *dw_cls, float *db_cls, float *scratch,
                   int64_t scratch_floats, frlw_stream_t stream);
+/* Which form a call of frlw_pred_fwd / frlw_pred_bwd with these sizes takes (host arithmetic only, nothing is launched):
+ * out = {CPL, NG, n_wg}, the template arguments of k_pred_fwd / k_pred_bwd (float4 chunks per lane, groups of 8 outputs) and
+ * the workgroups of the launch.  Returns what the compute entries return for these sizes (FRLW_OK, FRLW_ERR_ARG,
+ * FRLW_ERR_UNSUPPORTED; out untouched unless FRLW_OK); the launchers take their form from the same function. */
+int frlw_pred_plan(int64_t M, int C, int nc, int32_t out[3]);
 
 /* The pools of SPPBottleneck in training mode (network_blocks.py:139-151): out (B, H, W, 4C) NHWC = cat[x, maxpool5, maxpool9,
  * maxpool13] (stride 1, "same" padding, ATen's tie rule: the first maximum in row-major window order), argmax (B, H, W, 3, C)
@@ -639,6 +644,10 @@ int frlw_pred_bwd(const float *reg_feat, const float *cls_feat, const float *dou
  * The maps of 64, 32 or 16 channels must fit the LDS (H * W <= 512), else FRLW_ERR_UNSUPPORTED. */
 int frlw_spp_train_fwd(const float *x, int B, int H, int W, int C, float *out, uint16_t *argmax, frlw_stream_t stream);
 int frlw_spp_train_bwd(const float *dout, const uint16_t *argmax, int B, int H, int W, int C, float *dx, frlw_stream_t stream);
+/* The form of frlw_spp_train_fwd / frlw_spp_train_bwd for these sizes (host arithmetic only): out = {channels per workgroup
+ * (64, 32 or 16), dynamic LDS bytes of the forward, of the backward}.  Returns what the compute entries return for these
+ * sizes (out untouched unless FRLW_OK); the launchers take channel width, grid and LDS size from the same function. */
+int frlw_spp_train_plan(int B, int H, int W, int C, int32_t out[3]);
 
 /* ---------------------------------------------------------------------------------------------
  * SimOTA label assignment of the YOLOX training branch, whole batch, no host round trips.
