@@ -80,7 +80,8 @@ __device__ __forceinline__ void leaky_u8_lookup_n(const float (&v)[N], const uin
 // of 1/32 octave of x (the float's exponent and five mantissa bits) holds at most ONE threshold.  lut[b] = the level at the
 // bucket's upper end; the level of x is lut[b] + (x <= thr[lut[b] + 1]): one byte and one word from LDS, a compare and an add --
 // no transcendental, no first guess to repair.  Buckets start at 2^-6 (everything below shares bucket 0: level 254, or 255 for
-// x = 0, which thr[255] = 0 decides) and end at 2^13 (level 0 from 6002 on).  k_leaky_fill builds lut[] from thr[] itself and
+// x <= thr[255], which the compare decides; thr[255] is not 0 but 2.5928e-7 on gfx950, bits 0x348b3334: below it 1 - l / 8.7
+// rounds to 1) and end at 2^13 (level 0 from 6002 on).  k_leaky_fill builds lut[] from thr[] itself and
 // CHECKS the one-threshold property for every bucket on the device's own table (word kLeakyOkWord); a device whose log1pf broke
 // it would take the exact routine for every value.
 constexpr int kLeakyBucketShift = 18;                         // 5 mantissa bits
