@@ -5,7 +5,9 @@
 The model is built the way ``test.py`` builds it (``--exp_type``, ``--dataset``, ``--event_volume_bins``; ``--resume_exp E`` loads
 ``<log_path>E/checkpoints/best_epoch.pth``, ``--checkpoint`` any checkpoint file of this build or of the reference).  The events
 are encoded on the GPU as the TAF recipes expect them (``generate_taf.py``: K = 8, 10 ms windows) -- every frame of a detector
-batch in one encode call (``frlw_evd_amd.stream.StreamDetector``); no annotation file and no representation file is needed."""
+batch in one encode call (``frlw_evd_amd.stream.StreamDetector``); no annotation file and no representation file is needed.
+``--frames DIR [--frames_every N]`` also writes every N-th frame as a PNG, the TAF image with that frame's detections, painted on
+the GPU from the volumes the detector just read (``frlw_evd_amd.visualize``)."""
 import argparse
 import os
 import sys
@@ -31,6 +33,8 @@ def build_parser():
     parser.add_argument("--seq_nms", choices=("off", "stop", "skip"), default="off")   # Seq-NMS over the whole recording
     parser.add_argument("--seq_nms_metric", choices=("avg", "max"), default="avg")
     parser.add_argument("--seq_nms_drop", action="store_true")        # remove the boxes a sequence suppresses
+    parser.add_argument("--frames")                                   # a directory: one PNG per frame, <stem>_<t>.png
+    parser.add_argument("--frames_every", type=int, default=1)        # ... per every N-th frame
     parser.set_defaults(record=None, bbox_path=None, data_path=None, batch_size=1, num_cpu_workers=1, nodes=1, metric="none")
     return parser
 
@@ -41,6 +45,74 @@ def seq_nms_options(args):
     if args.seq_nms == "off":
         return None
     return {"isolated": args.seq_nms, "metric": args.seq_nms_metric, "drop_suppressed": bool(args.seq_nms_drop)}
+
+
+def frame_stem(dat_path):
+    """``<dir>/<sequence>_td.dat`` -> ``<sequence>``: what the frames' file names start with."""
+    stem = os.path.basename(dat_path)
+    stem = stem[:-4] if stem.endswith(".dat") else stem
+    return stem[:-3] if stem.endswith("_td") else stem
+
+
+class FrameWriter:
+    """``StreamDetector``'s ``on_volumes`` callback behind ``--frames``: every ``every``-th frame as ``<dir>/<stem>_<t>.png``, the
+    TAF image of all 2K channels (README 7) at the sensor shape with that frame's detections.  Without Seq-NMS the boxes are
+    final when the batch arrives: one fused render launch per detector batch.  With it they are final only after the whole
+    recording: the batches' backgrounds are rendered without boxes and kept on the host, and ``finish`` overlays the rescored boxes
+    that no sequence suppressed (``BGR`` mode) before it writes the files.  The box file may keep the suppressed boxes (no
+    ``--seq_nms_drop``), so ``finish`` runs Seq-NMS once more on the boxes it collected, with the drop switched on."""
+
+    def __init__(self, directory, stem, sensor, labelmap, every=1, seq_nms=None):
+        if every < 1:
+            raise SystemExit("--frames_every: at least 1")
+        self.directory, self.stem, self.sensor, self.labelmap, self.every = directory, stem, sensor, labelmap, int(every)
+        self.seq_nms = None if seq_nms is None else dict(seq_nms, drop_suppressed=True)
+        self.seen = 0
+        self.written = 0
+        self.backgrounds, self.stamps, self.rows = [], [], []
+        os.makedirs(directory, exist_ok=True)
+
+    def path(self, t):
+        return os.path.join(self.directory, "{0}_{1}.png".format(self.stem, int(t)))
+
+    def _write(self, images, stamps):
+        from frlw_evd_amd import visualize
+        for img, t in zip(images.cpu().numpy(), stamps):
+            visualize.write_png(self.path(t), img)
+            self.written += 1
+
+    def __call__(self, u8, enc, stamps, boxes):
+        import torch
+        from frlw_evd_amd import visualize
+        pick = [j for j in range(len(stamps)) if (self.seen + j) % self.every == 0]
+        self.seen += len(stamps)
+        self.rows += boxes                          # every frame's boxes: Seq-NMS links across the frames not drawn
+        if not pick:
+            return
+        vol = u8.reshape(u8.shape[0], -1, enc[0], enc[1])
+        if len(pick) != len(stamps):
+            vol = vol[torch.tensor(pick, device=vol.device)]
+        if self.seq_nms is None:
+            self._write(visualize.render(vol, "TAF", self.sensor, dt=[boxes[j] for j in pick], labelmap=self.labelmap),
+                        [stamps[j] for j in pick])
+        else:
+            self.backgrounds.append(visualize.render(vol, "TAF", self.sensor).cpu())
+            self.stamps += [(self.seen - len(stamps) + j, stamps[j]) for j in pick]
+
+    def finish(self):
+        """The Seq-NMS route's second half; nothing to do otherwise."""
+        if self.seq_nms is None or not self.stamps:
+            return
+        import torch
+        from frlw_evd_amd import visualize
+        from frlw_evd_amd.seq_nms import rescore_frames
+        rows, _ = rescore_frames(self.rows, **self.seq_nms)
+        backgrounds = torch.cat(self.backgrounds)
+        for lo in range(0, len(self.stamps), 64):
+            part = self.stamps[lo:lo + 64]
+            images = visualize.render(backgrounds[lo:lo + 64].cuda(), "BGR", self.sensor, dt=[rows[j] for j, _ in part],
+                                      labelmap=self.labelmap)
+            self._write(images, [t for _, t in part])
 
 
 def build_model(args):
@@ -72,15 +144,26 @@ def main(argv=None):
     net, settings = build_model(args)
     sensor, _ = SHAPES["gen4" if args.dataset == "gen4" else "gen1"]
     f_event = dat_io.DatFile(args.dat)
+    writer = None
+    if args.frames is not None:
+        from frlw_evd_amd.visualize import LABELMAPS
+        writer = FrameWriter(args.frames, frame_stem(args.dat), sensor, LABELMAPS["gen4" if args.dataset == "gen4" else "gen1"],
+                             args.frames_every, seq_nms_options(args))
     det = StreamDetector(net, sensor, settings.img_size, dataset=args.dataset, volume_bins=8, input_bins=args.event_volume_bins,
-                         period_us=args.period, frames_per_call=args.frames_per_call, seq_nms=seq_nms_options(args))
+                         period_us=args.period, frames_per_call=args.frames_per_call, seq_nms=seq_nms_options(args),
+                         on_volumes=writer)
     t_end = f_event.total_time() if args.t_end is None else args.t_end
     boxes = det.run(f_event.to_device(device=settings.gpu_device), args.t_begin, t_end)
+    if writer is not None:
+        writer.finish()
     path = args.out if args.out.endswith(".npy") else args.out + ".npy"
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     np.save(path, boxes)
-    print({"frames": len(det.frame_times(args.t_begin, t_end)), "boxes": int(len(boxes)), "sequences": int(det.sequences),
-           "out": path})
+    summary = {"frames": len(det.frame_times(args.t_begin, t_end)), "boxes": int(len(boxes)), "sequences": int(det.sequences),
+               "out": path}
+    if writer is not None:
+        summary["frames_written"] = writer.written
+    print(summary)
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
     return boxes

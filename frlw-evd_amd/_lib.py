@@ -24,6 +24,9 @@ TVL1_MAX_LEVELS = 8
 SEQ_NMS_MAX_FRAMES = 4096
 SEQ_NMS_MAX_BOXES = 64
 SEQ_NMS_TRUNCATED = 1   # status bit: the selection loop ended at max_sequences
+RENDER_MAX_FRAMES = 64
+RENDER_MAX_BOXES = 512
+RENDER_MODES = ("TAF", "SAE", "ECI", "EV", "BGR")   # the FRLW_RENDER_* enum, in order
 
 # the FRLW_CONV_PATH_* counters of frlw_conv_path_counts, in the header's enum order (lower case, prefix dropped)
 CONV_PATHS = ("128x32", "128x128_4x1", "128x128_2x2", "64x128", "64x64", "split_vec", "split_scalar", "split_inkernel",
@@ -166,6 +169,8 @@ SYMBOLS = {
     "frlw_resize_nearest_f32": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "frlw_resize_nearest_u8": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "frlw_quantize_u8": (_I, [_P, _I64, _I, _P, _P]),
+    "frlw_render_frames": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, C.POINTER(C.c_int32), _P, _P]),
+    "frlw_hsv_to_bgr_u8": (_I, [_P, _P, _I64, _P]),
     "frlw_det_create": (_P, []),
     "frlw_det_destroy": (None, [_P]),
     "frlw_det_num_ops": (_I, [_P]),

@@ -38,10 +38,7 @@ __global__ void k_resize_nearest(const T *in, int C, int H, int W, int Ho, int W
         const int xo = (int)(o % Wo);
         const int yo = (int)((o / Wo) % Ho);
         const int c = (int)(o / ((long long)Wo * Ho));
-        int ys = (int)floorf((float)yo * sh);
-        int xs = (int)floorf((float)xo * sw);
-        if (ys > H - 1) ys = H - 1;
-        if (xs > W - 1) xs = W - 1;
+        const int ys = nearest_src(yo, sh, H), xs = nearest_src(xo, sw, W);
         out[o] = in[((long long)c * H + ys) * W + xs];
     }
 }
@@ -61,9 +58,7 @@ __global__ void k_sample_transform(const uint8_t *in, int B, int C, int H, int W
         const int Hr = p[0], Wr = p[1], y0 = p[2], x0 = p[3], flip = p[4];
         const int xs = flip ? W - 1 - x : x; // img[:, :, ::-1] after the crop
         const float sh = (float)H / (float)Hr, sw = (float)W / (float)Wr;
-        int sy = (int)floorf((float)(y + y0) * sh), sx = (int)floorf((float)(xs + x0) * sw);
-        if (sy > H - 1) sy = H - 1;
-        if (sx > W - 1) sx = W - 1;
+        const int sy = nearest_src(y + y0, sh, H), sx = nearest_src(xs + x0, sw, W);
         out[o] = (float)in[(bc * H + sy) * W + sx] / 255.0f;
     }
 }

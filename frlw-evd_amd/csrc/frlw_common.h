@@ -95,6 +95,14 @@ __device__ __forceinline__ uint8_t f32_to_u8(float v)
     return (uint8_t)i;
 }
 
+// Source index of torch's interpolate(mode='nearest'): min(floor(dst * scale), in - 1) with scale = float(in) / float(out).
+// The one statement of the rule: the resize and sample-transform kernels of elementwise.hip and the renderer (render.hip).
+__device__ __forceinline__ int nearest_src(int dst, float scale, int in_size)
+{
+    const int s = (int)floorf((float)dst * scale);
+    return s > in_size - 1 ? in_size - 1 : s;
+}
+
 // ---- host side: what partition_events hands to the tile launch (leaky_thr: TAF only, the per-device threshold table of leaky.hip)
 struct Partitioned { const uint2 *records; const uint32_t *base; WsHeader *hdr; const uint32_t *leaky_thr; Plan plan; };
 

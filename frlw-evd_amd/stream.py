@@ -29,10 +29,13 @@ class StreamDetector:
     K / 2 slots).  A frame every ``period_us``, a multiple of the FIFO window ``window_us``; ``frames_per_call`` frames (at most
     64) per encode call and per detector batch.  ``seq_nms``: None, or a dict of ``seq_nms.rescore_frames`` arguments (``isolated``,
     ``metric``, ``drop_suppressed``, thresholds): ``run`` then links the boxes of the whole recording, writes the rescored
-    confidences and the sequence ids (``track_id``) and leaves the number of sequences in ``self.sequences``."""
+    confidences and the sequence ids (``track_id``) and leaves the number of sequences in ``self.sequences``.  ``on_volumes``: None,
+    or a callable ``run`` calls once per detector batch with ``(u8, enc, stamps, boxes)`` -- the batch's uint8 volumes
+    (S, K, 2, h, w) at the encode shape ``enc``, still on the GPU, the frames' timestamps and their boxes before any Seq-NMS
+    (``visualize.render`` draws from exactly this)."""
 
     def __init__(self, model, sensor_shape, img_size, dataset="gen1", volume_bins=8, input_bins=8, period_us=50000,
-                 window_us=10000, frames_per_call=32, seq_nms=None):
+                 window_us=10000, frames_per_call=32, seq_nms=None, on_volumes=None):
         self.model = model
         self.sensor_shape = (int(sensor_shape[0]), int(sensor_shape[1]))
         self.img_size = (int(img_size[0]), int(img_size[1]))
@@ -52,6 +55,7 @@ class StreamDetector:
         self.dataset = dataset
         self.seq_nms = None if seq_nms is None else dict(seq_nms)
         self.sequences = 0
+        self.on_volumes = on_volumes
         self.evaluator = evaluator(None, self.frames_per_call, 10000, self.sensor_shape[1], self.sensor_shape[0], self.img_size[1],
                                    self.img_size[0], dataset)
 
@@ -108,7 +112,10 @@ class StreamDetector:
                                          [bins] * len(stamps), self.K, flip_k=True, xmap=xmap, ymap=ymap)
                 with torch.no_grad():
                     outputs = self.model.detect(self.hand_off(u8, enc))
-                out += self.boxes(outputs, stamps)
+                found = self.boxes(outputs, stamps)
+                if self.on_volumes is not None:
+                    self.on_volumes(u8, enc, stamps, found)
+                out += found
         if self.seq_nms is not None:
             from .seq_nms import rescore_frames
             out, self.sequences = rescore_frames(out, **self.seq_nms)

@@ -901,6 +901,32 @@ int frlw_baseconv_train_bwd(const float *dy, int64_t dy_row_stride, const float 
                             const float *w_cache, void *scratch, int64_t scratch_bytes, int *splitk_counters,
                             const frlw_baseconv_fuse_t *fuse, int precision, frlw_stream_t stream);
 
+/* ---- Visualization (csrc/render.hip): representation -> colour image -> boxes and tags, one launch per batch.
+ *
+ * frlw_render_frames paints n <= FRLW_RENDER_MAX_FRAMES frames.  src: uint8 volumes (n, C, h, w) at the stored shape, sampled to
+ * the output shape (H, W) by the nearest rule of frlw_resize_nearest_u8, or -- mode FRLW_RENDER_BGR -- ready backgrounds
+ * (n, H, W, 3) (then C = 3, h = H, w = W).  Backgrounds: TAF (C even, >= 2), SAE (C >= 1), ECI (C = 2), EV (C even, >= 2) as
+ * DESIGN.md 3.16 defines them.  boxes: a DEVICE array of 32-byte records, box_offsets: a HOST array of n + 1 non-decreasing
+ * offsets into it (frame i owns [box_offsets[i], box_offsets[i + 1]), at most FRLW_RENDER_MAX_BOXES of them); boxes may be NULL
+ * when there is none.  A frame's boxes apply in array order, the last hit wins; per box: outline, tag fill, glyphs.  out:
+ * (n, H, W, 3) uint8 BGR, must not overlap src.  Every output byte is written by exactly one thread: no atomics, bit-deterministic
+ * alone or batched.  Argument errors (FRLW_ERR_ARG) are found on the host before anything is launched. */
+#define FRLW_RENDER_MAX_FRAMES 64
+#define FRLW_RENDER_MAX_BOXES 512
+enum { FRLW_RENDER_TAF = 0, FRLW_RENDER_SAE = 1, FRLW_RENDER_ECI = 2, FRLW_RENDER_EV = 3, FRLW_RENDER_BGR = 4 };
+typedef struct frlw_render_box {
+    int32_t x1, y1, x2, y2;  /* inclusive corners, each within +-2^20 */
+    uint8_t kind;            /* 0 ground truth, 1 detection: colour and tag width */
+    uint8_t n_label, n_score, reserved;
+    uint8_t label[8];        /* n_label <= 5 characters of the class name (a-z, 0-9, '.'; anything else is blank) */
+    uint8_t score[4];        /* n_score <= 4 characters of the confidence */
+} frlw_render_box_t;
+int frlw_render_frames(const uint8_t *src, int n, int C, int h, int w, int mode, int H, int W, const frlw_render_box_t *boxes,
+                       const int32_t *box_offsets, uint8_t *out, frlw_stream_t stream);
+/* (n_pixels, 3) uint8 H, S, V -> B, G, R by the conversion the TAF / SAE / EV backgrounds go through (H in units of 2 degrees,
+ * values above 180 wrap). */
+int frlw_hsv_to_bgr_u8(const uint8_t *hsv, uint8_t *bgr, int64_t n_pixels, frlw_stream_t stream);
+
 /* Measurement aid: a bare loop of v_mfma_f32_32x32x2_f32 (the instruction of every convolution here) on `blocks`
  * workgroups of four wavefronts, iters x 32 MFMAs (= iters x 131072 FLOP) per wavefront, operands = the 256 floats of
  * `seed` (device).  Timed by the caller (bench.py): the fp32 matrix rate the chip SUSTAINS on non-trivial data, which is
