@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Detect on a raw recording: ``--dat <file>_td.dat`` -> ``<out>.npy``, a structured box array with the fields of a
+"""Detect on a raw recording: ``--dat <file>_td.dat`` or ``--raw <file>.raw`` -> ``<out>.npy``, a structured box array with the fields of a
 ``*_bbox.npy`` annotation file (``dataset.read_boxes`` reads it back), one set of boxes every ``--period`` microseconds.
 
 The model is built the way ``test.py`` builds it (``--exp_type``, ``--dataset``, ``--event_volume_bins``; ``--resume_exp E`` loads
@@ -7,7 +7,10 @@ The model is built the way ``test.py`` builds it (``--exp_type``, ``--dataset``,
 are encoded on the GPU as the TAF recipes expect them (``generate_taf.py``: K = 8, 10 ms windows) -- every frame of a detector
 batch in one encode call (``frlw_evd_amd.stream.StreamDetector``); no annotation file and no representation file is needed.
 ``--frames DIR [--frames_every N]`` also writes every N-th frame as a PNG, the TAF image with that frame's detections, painted on
-the GPU from the volumes the detector just read (``frlw_evd_amd.visualize``)."""
+the GPU from the volumes the detector just read (``frlw_evd_amd.visualize``).
+``--raw`` takes a Prophesee EVT 3.0 recording as the camera wrote it: the words are decoded to event records on the GPU
+(``frlw_evd_amd.raw_io``), the sensor shape comes from the file's header (``--dataset`` names it when the header does not), and the
+printed summary carries the decode counters."""
 import argparse
 import os
 import sys
@@ -15,9 +18,26 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
+def recording_source(args):
+    """``("dat" | "raw", path)``: exactly one of ``--dat`` / ``--raw`` names the recording."""
+    if (args.dat is None) == (args.raw is None):
+        raise SystemExit("exactly one of --dat FILE_td.dat / --raw FILE.raw names the recording")
+    return ("dat", args.dat) if args.raw is None else ("raw", args.raw)
+
+
+class _Parser(argparse.ArgumentParser):
+    """The check that one recording is named runs behind the parse (neither flag is ``required``)."""
+
+    def parse_args(self, args=None, namespace=None):
+        parsed = super().parse_args(args, namespace)
+        recording_source(parsed)
+        return parsed
+
+
 def build_parser():
-    parser = argparse.ArgumentParser(description="Detect on a raw .dat recording.")
-    parser.add_argument("--dat", required=True)          # <sequence>_td.dat
+    parser = _Parser(description="Detect on a raw .dat or EVT 3.0 .raw recording.")
+    parser.add_argument("--dat")                         # <sequence>_td.dat
+    parser.add_argument("--raw")                         # <sequence>.raw (Prophesee EVT 3.0), instead of --dat
     parser.add_argument("--out", required=True)          # written as <out>.npy
     parser.add_argument("--local_rank", "--local-rank", type=int, default=None)
     parser.add_argument("--resume_exp")
@@ -50,7 +70,7 @@ def seq_nms_options(args):
 def frame_stem(dat_path):
     """``<dir>/<sequence>_td.dat`` -> ``<sequence>``: what the frames' file names start with."""
     stem = os.path.basename(dat_path)
-    stem = stem[:-4] if stem.endswith(".dat") else stem
+    stem = stem[:-4] if stem.endswith((".dat", ".raw")) else stem
     return stem[:-3] if stem.endswith("_td") else stem
 
 
@@ -143,17 +163,30 @@ def main(argv=None):
     from frlw_evd_amd.stream import StreamDetector
     net, settings = build_model(args)
     sensor, _ = SHAPES["gen4" if args.dataset == "gen4" else "gen1"]
-    f_event = dat_io.DatFile(args.dat)
+    kind, rec_path = recording_source(args)
+    decode_counters = None
+    if kind == "raw":
+        from frlw_evd_amd import raw_io
+        f_event = raw_io.RawFile(rec_path)
+        sensor = f_event.size or sensor
+        records, decode_counters = f_event.decode(device=settings.gpu_device, time_shift=True, size=sensor)
+        if decode_counters["unsorted"] > 0:
+            raise SystemExit("{0}: {1} events are earlier than their predecessor; the detector needs time-sorted records "
+                             "(sorting is not done here)".format(rec_path, decode_counters["unsorted"]))
+    else:
+        f_event = dat_io.DatFile(rec_path)
     writer = None
     if args.frames is not None:
         from frlw_evd_amd.visualize import LABELMAPS
-        writer = FrameWriter(args.frames, frame_stem(args.dat), sensor, LABELMAPS["gen4" if args.dataset == "gen4" else "gen1"],
+        writer = FrameWriter(args.frames, frame_stem(rec_path), sensor, LABELMAPS["gen4" if args.dataset == "gen4" else "gen1"],
                              args.frames_every, seq_nms_options(args))
     det = StreamDetector(net, sensor, settings.img_size, dataset=args.dataset, volume_bins=8, input_bins=args.event_volume_bins,
                          period_us=args.period, frames_per_call=args.frames_per_call, seq_nms=seq_nms_options(args),
                          on_volumes=writer)
     t_end = f_event.total_time() if args.t_end is None else args.t_end
-    boxes = det.run(f_event.to_device(device=settings.gpu_device), args.t_begin, t_end)
+    if kind == "dat":
+        records = f_event.to_device(device=settings.gpu_device)
+    boxes = det.run(records, args.t_begin, t_end)
     if writer is not None:
         writer.finish()
     path = args.out if args.out.endswith(".npy") else args.out + ".npy"
@@ -163,6 +196,8 @@ def main(argv=None):
                "out": path}
     if writer is not None:
         summary["frames_written"] = writer.written
+    if decode_counters is not None:
+        summary["decode"] = decode_counters
     print(summary)
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()

@@ -165,6 +165,11 @@ SYMBOLS = {
     "frlw_seq_nms_workspace_bytes": (_SZ, [_I64, _I64, _I]),
     "frlw_seq_nms": (_I, [_P, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, C.c_double, C.c_double, _I, _I, _I, _P, _P, _P, _P,
                          _P, _SZ, _P]),
+    "frlw_evt3_workspace_bytes": (_SZ, [_I64]),
+    "frlw_evt3_geometry": (_I, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "frlw_evt3_count": (_I, [_P, _I64, _I, _I, _P, _P, _SZ, _P]),
+    "frlw_evt3_emit": (_I, [_P, _I64, _I, _I, _P, _SZ, _P, _I64, _I, _P]),
+    "frlw_evt3_result": (_I, [_P, _P, _P, _P, C.POINTER(C.c_int)]),
     "frlw_leaky_transform": (_I, [_P, _I64, _P, _P, _P]),
     "frlw_resize_nearest_f32": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "frlw_resize_nearest_u8": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),

@@ -38,6 +38,34 @@ def synth_events(seed: int, n: int, width: int, height: int, t_span: int,
     return {"x": x, "y": y, "p": p, "t": t}
 
 
+def synth_burst_events(seed: int, n: int, width: int, height: int, t_span: int, burst_fraction: float = 0.5,
+                       t_offset: int = 0):
+    """About ``n`` events as ``synth_events`` returns them, of which about ``burst_fraction`` come in bursts: 2 to 30 events
+    of one ``(t, y, p)`` with ascending x inside a span of 40 pixels (what a moving edge gives a row-wise sensor readout, and
+    what the EVT 3.0 vector words exist for -- uniform pixels alone give almost no such runs).  Time-sorted; a burst stays
+    contiguous.  ``width`` must be at least 40."""
+    rng = np.random.default_rng(seed)
+    n_burst_events = int(n * burst_fraction)
+    lens = rng.integers(2, 31, size=max(1, n_burst_events // 16 + 1), dtype=np.int64)
+    lens = lens[:int(np.searchsorted(np.cumsum(lens), n_burst_events, side="right"))]
+    nb = len(lens)
+    ns = max(0, n - int(lens.sum()))
+    # the bursts' pixels: the `len` smallest of 40 random keys per burst, in ascending x
+    chosen = np.argsort(np.argsort(rng.random((nb, 40)), axis=1), axis=1) < lens[:, None]
+    bx = (rng.integers(0, width - 39, size=nb, dtype=np.int64)[:, None] + np.arange(40)[None, :])[chosen]
+    item_len = np.concatenate([np.ones(ns, np.int64), lens])
+    item_t = rng.integers(0, t_span, size=ns + nb, dtype=np.int64) + int(t_offset)
+    item_y = rng.integers(0, height, size=ns + nb, dtype=np.int64)
+    item_p = rng.integers(0, 2, size=ns + nb, dtype=np.int64)
+    src_x = np.concatenate([rng.integers(0, width, size=ns, dtype=np.int64), bx])
+    src_start = np.concatenate([[0], np.cumsum(item_len)[:-1]]) if ns + nb else np.zeros(0, np.int64)
+    order = np.argsort(item_t, kind="stable")
+    ln = item_len[order]
+    item_of = np.repeat(order, ln)
+    within = np.arange(int(ln.sum()), dtype=np.int64) - np.repeat(np.cumsum(ln) - ln, ln)
+    return {"x": src_x[src_start[item_of] + within], "y": item_y[item_of], "p": item_p[item_of], "t": item_t[item_of]}
+
+
 def to_xytp_f64(ev, t=None) -> np.ndarray:
     """``(N, 4)`` float64 ``[x, y, t, p]``; ``t`` may be overridden (e.g. pre-normalised)."""
     tt = ev["t"] if t is None else t

@@ -453,6 +453,53 @@ int frlw_seq_nms(const float *boxes, const double *scores, const int32_t *labels
                  int max_sequences, double *out_scores, int32_t *out_seq, uint8_t *out_flags, int32_t *status, void *workspace,
                  size_t workspace_bytes, frlw_stream_t stream);
 
+/*
+ * Prophesee EVT 3.0 words -> FRLW_LAYOUT_DAT8 records (csrc/evt3.hip), as DESIGN.md's "EVT 3.0 decode" section defines the format
+ * and tests/evt3_restated.py restates it.  words: DEVICE, little-endian 16-bit words (any 2-byte alignment; 16-byte alignment is
+ * the fast case), at most 2^31 per call; width / height in 1..2048.  A longer stream is decoded piece by piece with the state
+ * carried; the cut may fall anywhere, also inside a vector run.
+ *
+ * frlw_evt3_count   enqueues four launches that leave in the workspace: the plan (per chunk of words its carried-in state and the
+ *                   offset of its first record), the counters and the carried-out state.  state_in: HOST, NULL = start of stream.
+ * frlw_evt3_result  synchronises `stream` and copies counters, carried-out state (may be NULL) and the data-dependent status to
+ *                   the host.  Between the two calls the caller reads counters.events to size `out`; after frlw_evt3_emit it reads
+ *                   the status: FRLW_ERR_SPAN a t does not fit 32 bits (or lies below the shift), FRLW_ERR_ARG capacity below
+ *                   counters.events -- NOTHING is written in either case; FRLW_ERR_HIP the words are not the ones counted.
+ * frlw_evt3_emit    one launch: the same words, n_words, width, height and workspace again; out: DEVICE, capacity records of 8
+ *                   bytes, never written at or beyond capacity; time_shift != 0 subtracts (first EVT_TIME_HIGH of the stream) << 12
+ *                   from every t.  Records come out in stream order, each written once.
+ * Counters: t values are unshifted.  No kernel waits on another workgroup; no host synchronisation outside frlw_evt3_result.
+ * frlw_evt3_workspace_bytes and frlw_evt3_geometry (words per workgroup chunk and per lane piece) are HOST only; 0 = n_words
+ * negative or over the limit.  NULL pointers, a width or height outside 1..2048, a wrong struct_size: FRLW_ERR_ARG; a short
+ * workspace: FRLW_ERR_WORKSPACE; nothing is enqueued in either case.
+ */
+typedef struct frlw_evt3_state {
+    int32_t struct_size; /* sizeof(frlw_evt3_state_t) */
+    int32_t reserved;
+    uint32_t flags;      /* bit 0 TIME_HIGH seen, 1 TIME_LOW seen, 2 ADDR_Y seen, 3 VECT_BASE_X seen, 4 its polarity */
+    uint32_t loops;      /* clock wraps so far */
+    uint32_t first_high; /* first EVT_TIME_HIGH of the stream */
+    uint32_t last_high;
+    uint32_t low_y;      /* last EVT_TIME_LOW | last EVT_ADDR_Y << 16 */
+    uint32_t base;       /* x of the next vector word's bit 0 */
+    uint32_t has_last_t; /* an event was emitted so far ... */
+    uint32_t reserved2;
+    uint64_t last_t;     /* ... and its t */
+} frlw_evt3_state_t;
+typedef struct frlw_evt3_counters {
+    int32_t struct_size; /* sizeof(frlw_evt3_counters_t) */
+    int32_t reserved;
+    uint64_t events, before_sync, out_of_frame, triggers, other_words, time_loops, unsorted, first_t, last_t, min_t, max_t;
+} frlw_evt3_counters_t;
+size_t frlw_evt3_workspace_bytes(int64_t n_words);
+int frlw_evt3_geometry(int *chunk_words, int *lane_words);
+int frlw_evt3_count(const uint16_t *words, int64_t n_words, int width, int height, const frlw_evt3_state_t *state_in, void *workspace,
+                    size_t workspace_bytes, frlw_stream_t stream);
+int frlw_evt3_emit(const uint16_t *words, int64_t n_words, int width, int height, void *workspace, size_t workspace_bytes, void *out,
+                   int64_t capacity, int time_shift, frlw_stream_t stream);
+int frlw_evt3_result(const void *workspace, frlw_stream_t stream, frlw_evt3_counters_t *counters, frlw_evt3_state_t *state_out,
+                     int *status_out);
+
 /* The verdict of the one-time LDS lane-order self-test of the fast paths (frlw_taf_encode_batch, frlw_ev_encode_batch, the
  * two-launch forms of frlw_sae_encode / frlw_eci_encode) for the CURRENT device: *ok_out = 1 when the property held, 0 when
  * it did not (those entry points then answer FRLW_ERR_UNSUPPORTED and callers take the general path -- same bits, different
