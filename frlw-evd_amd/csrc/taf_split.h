@@ -1,7 +1,8 @@
 // taf_split.h -- the second level: a tile's records sub-tile-major, stably (kf_split_whole, the segment kernels kf_split_place and
 // kf_segcount_cm); TileP, the kernel argument it shares with the walk.
-// Expects taf_decode.h (FastHeader), taf_partition.h (whole_max_of, split_segments) and taf_column.h.
+// Expects taf_decode.h (FastHeader), taf_partition.h (whole_max_of, split_segments), taf_column.h and taf_blocktab.h.
 #pragma once
+#include "taf_blocktab.h"
 #include "taf_column.h"
 #include "taf_partition.h"
 #include <type_traits>
@@ -103,8 +104,9 @@ template <bool CM>
 __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(8, 8))) void kf_split_whole(TileP q, CmP cm, SeqTab S) // (64 VGPRs: two workgroups per CU)
 {
     constexpr int RPT = kSplitSeg / kFT; // 8 records per thread and chunk of 8192
+    constexpr int kBtGroup = 4;          // table entries (and record loads) a thread has in flight at a time in step 1
     // scnt [sub-tile][batch] tickets, then exclusive prefixes | stage: one chunk of records, sub-tile-major.  CM, while the
-    // list is gathered (before either is used): the column L | D | the position index
+    // list is gathered (before either is used): the column L | D | the block address table (or the position index)
     // CM: the column lies over the STAGING area (+ a tail of its own), not over the counters: the counters are zeroed in front of
     // the gather and the tickets are taken as the gathered records arrive -- no barrier, no drained load queue in between
     constexpr int kColWords = 2 * kColMax + 1 + kSplitWhole / 32 + 1;
@@ -140,9 +142,14 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     uint32_t beg, n;
     uint32_t m[kWholeChunks][RPT];
     if (CM) {
-        uint32_t *colL = stage, *colD = stage + kColMax + 1;
-        uint16_t *idx = (uint16_t *)(stage + 2 * kColMax + 1);
         const int s = g / q.T, C = S.chunk0[s + 1] - S.chunk0[s];
+        // The usual call (a sequence of at most kBtCols chunks, fewer than 2^28 records): L | D | the block address table
+        // (taf_blocktab.h) in 24 KB of the staging area; otherwise the column at its full length and the position index behind it
+        const bool tabled = C <= frlw_bt::kBtCols && S.ev0[S.n_seq] - S.ev0[0] < (1ll << 28); // (kernel argument: uniform)
+        static_assert(2 * frlw_bt::kBtCols + 2 + kSplitWhole / 16 * 2 <= kSplitSeg, "column + table inside the staging area");
+        uint32_t *colL = stage, *colD = stage + (tabled ? frlw_bt::kBtCols : kColMax) + 1;
+        uint16_t *idx = (uint16_t *)(stage + 2 * kColMax + 1);
+        frlw_bt::BtEntry *tab = (frlw_bt::BtEntry *)(stage + 2 * frlw_bt::kBtCols + 2); // (8-byte aligned: stage is, at 16)
         for (int i = tid; i < kFW * kWholeRow; i += kFT) scnt[i] = 0u; // (published by the barriers of col_load)
         // (readfirstlane: the workgroup-uniform values that come out of LDS are uniform for the COMPILER too -- as vector values
         // they turned every "is this chunk of the list there at all" test below into divergent control flow, and 19 of the 32
@@ -173,17 +180,56 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                 if (first + k < (uint32_t)cm.max_segs) cm.segdesc[first + k] = (uint32_t)g;
             return;
         }
-        col_index<kFT>(colL, C, 0u, n, idx);
+        if (tabled) {
+            for (int c = tid; c < C; c += kFT) frlw_bt::bt_build_run(colL, colD, C, c, n, tab);
+        } else {
+            col_index<kFT>(colL, C, 0u, n, idx);
+        }
         __syncthreads();
         const uint32_t wvs = (uint32_t)__builtin_amdgcn_readfirstlane(wv); // (the wavefront index as a scalar: uniform branches below)
-        // 1. the whole list into registers: list position -> chunk through the index + a walk over at most a few run boundaries
-        // (two sweeps: every index first -- LDS work only, nothing in flight -- then the loads through one buffer descriptor with
-        // 32-bit offsets: with 64-bit addresses next to the 32 records the compiler spilled 19 of them, each spill waiting for
-        // its load)
+        // 1. the whole list into registers: list position -> address through the block table (without one: chunk through the index + a
+        // walk over at most a few run boundaries); the loads go through one buffer descriptor with 32-bit offsets: with 64-bit
+        // addresses next to the 32 records the compiler spilled 19 of them, each spill waiting for its load
         {
             const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)cm.rec, 0, 0xffffffffu, 0x00020000);
+            // (a staging chunk the list does not reach issues no load at all -- a 22 000-record tile has three of the four; its m[c][.]
+            // stay unset and unread: every later step tests the same bound)
+            if (tabled) {
+#pragma unroll
+                for (int c = 0; c < kWholeChunks; ++c) {
+                    if ((uint32_t)(c * kSplitSeg) >= n) break; // workgroup-uniform
+                    // one 8-byte entry per 16 positions: no index, no walk (and no scalar search for a single run either: that is two
+                    // dependent LDS trips per wave-instruction where this is one read).  Four entries are read together, then their
+                    // four loads go out; lanes behind the list's end take its last record's entry (clamped: it exists)
+#pragma unroll
+                    for (int u0 = 0; u0 < RPT; u0 += kBtGroup) {
+                        frlw_bt::BtEntry e[kBtGroup];
+                        uint32_t ic[kBtGroup], wmax = 0u;
+#pragma unroll
+                        for (int k = 0; k < kBtGroup; ++k) {
+                            const uint32_t i = (uint32_t)(c * kSplitSeg + (u0 + k) * kFT + tid);
+                            ic[k] = i < n ? i : n - 1u;
+                            e[k] = tab[ic[k] >> 4];
+                        }
+#pragma unroll
+                        for (int k = 0; k < kBtGroup; ++k) wmax = e[k].w > wmax ? e[k].w : wmax;
+                        if (__builtin_expect(__ballot(wmax == frlw_bt::kBtFallback) == 0ull, 1)) {
+#pragma unroll
+                            for (int k = 0; k < kBtGroup; ++k)
+                                m[c][u0 + k] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)(frlw_bt::bt_addr(e[k], ic[k]) << 2), 0, 0);
+                        } else { // a block with two run boundaries (runs shorter than 16 records, a skewed neighbour): those lanes walk the column
+#pragma unroll
+                            for (int k = 0; k < kBtGroup; ++k) {
+                                const uint32_t off = e[k].w == frlw_bt::kBtFallback ? frlw_bt::bt_walk(colL, colD, e[k].a, ic[k]) : frlw_bt::bt_addr(e[k], ic[k]);
+                                m[c][u0 + k] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)(off << 2), 0, 0);
+                            }
+                        }
+                    }
+                }
+            } else {
 #pragma unroll
             for (int c = 0; c < kWholeChunks; ++c) {
+                if ((uint32_t)(c * kSplitSeg) >= n) break; // workgroup-uniform
 #pragma unroll
                 for (int u = 0; u < RPT; ++u) {
                     const uint32_t i = (uint32_t)(c * kSplitSeg + u * kFT + tid), ic = i < n ? i : n - 1u;
@@ -201,6 +247,7 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                     }
                     m[c][u] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)(off << 2), 0, 0);
                 }
+            }
             }
         }
         beg = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_start);

@@ -82,11 +82,17 @@ __global__ __launch_bounds__(kWalkThreads) __attribute__((amdgpu_waves_per_eu(8,
     const uint32_t mul_bad0 = q.hdr->mul_bad;
     uint32_t beg = 0u, end = 0u;
     uint32_t wtab = 0u; // 1 / 2: kf_split_whole<true> has left this tile's window starts / found its list unsorted (TileP::wst_flag)
+    uint32_t fw_row = 0xffffffffu; // this lane's entry of the list's row of TileP::wst (meaningless while wtab == 0)
     if (!CMD) {
         // (sub[] of the NEXT pair is only written if that pair went through a split kernel: take the tile's own end)
         beg = q.sub[sg];
         end = q.sub_end ? q.sub_end[sg] : ((sub == kFW - 1 && !q.direct) ? q.base[g + 1] : q.sub[sg + 1]);
-        if (q.wst) wtab = q.wst_flag[g];
+        if (q.wst) {
+            wtab = q.wst_flag[g];
+            // the list's row of the window table rides with the header words (lane = window; the lanes behind the last one repeat entry n_windows): its address
+            // is the plan's, whatever the flag says -- loaded behind the flag it was a second dependent trip in front of the list
+            fw_row = q.wst[(long long)sg * (q.n_windows + 1) + (lane < q.n_windows ? lane : q.n_windows)];
+        }
     }
     if (status0 != 0) return; // data-dependent error: nothing is written (the caller re-runs the general path)
     WPROF_INIT();
@@ -180,13 +186,9 @@ __global__ __launch_bounds__(kWalkThreads) __attribute__((amdgpu_waves_per_eu(8,
     }
     if (!CMD && wtab != 0u) { // workgroup-uniform
         // lane = window: records of the list in front of window `lane` (window-sorted list); entry NW = all of them
-        const uint32_t *wrow = q.wst + (long long)sg * (NW + 1);
-        const uint32_t fw0 = wrow[lane < NW ? lane : NW];
-        // the list's lines are requested while the table row is on its way (one word per 128-byte line and thread: 16 384 records
-        // per round); phase 1's loads, which wait for the row, then find them in the caches
-        uint32_t list_touch = 0u;
-        for (uint32_t i = beg + 32u * (uint32_t)tid; i < end; i += 32u * kWalkThreads) list_touch |= list[i];
-        asm volatile("" ::"v"(list_touch));
+        const uint32_t fw0 = fw_row;
+        // (until the row came with the header words, a loop here requested one word of every line of the list while the row was
+        // on its way; with nothing in front of phase 1's loads any more it only cost its instructions: 52.2 -> 51.5 us without)
         first_w = fw0 != 0xffffffffu ? beg + fw0 : end; // what the scan leaves in wstart[]
         nonempty = __ballot(lane < NW && fw0 != 0xffffffffu);
         general = wtab == 2u;
