@@ -8,9 +8,9 @@ are encoded on the GPU as the TAF recipes expect them (``generate_taf.py``: K = 
 batch in one encode call (``frlw_evd_amd.stream.StreamDetector``); no annotation file and no representation file is needed.
 ``--frames DIR [--frames_every N]`` also writes every N-th frame as a PNG, the TAF image with that frame's detections, painted on
 the GPU from the volumes the detector just read (``frlw_evd_amd.visualize``).
-``--raw`` takes a Prophesee EVT 3.0 recording as the camera wrote it: the words are decoded to event records on the GPU
-(``frlw_evd_amd.raw_io``), the sensor shape comes from the file's header (``--dataset`` names it when the header does not), and the
-printed summary carries the decode counters."""
+``--raw`` takes a Prophesee recording as the camera wrote it, in the EVT 2.0, EVT 2.1 or EVT 3.0 encoding (the file's header names
+it): the words are decoded to event records on the GPU (``frlw_evd_amd.raw_io``), the sensor shape comes from the file's header
+(``--dataset`` names it when the header does not), and the printed summary carries the decode counters."""
 import argparse
 import os
 import sys
@@ -35,9 +35,9 @@ class _Parser(argparse.ArgumentParser):
 
 
 def build_parser():
-    parser = _Parser(description="Detect on a raw .dat or EVT 3.0 .raw recording.")
+    parser = _Parser(description="Detect on a raw .dat or Prophesee .raw (EVT 2.0, EVT 2.1, EVT 3.0) recording.")
     parser.add_argument("--dat")                         # <sequence>_td.dat
-    parser.add_argument("--raw")                         # <sequence>.raw (Prophesee EVT 3.0), instead of --dat
+    parser.add_argument("--raw")                         # <sequence>.raw (Prophesee EVT 2.0 / 2.1 / 3.0), instead of --dat
     parser.add_argument("--out", required=True)          # written as <out>.npy
     parser.add_argument("--local_rank", "--local-rank", type=int, default=None)
     parser.add_argument("--resume_exp")

@@ -38,6 +38,7 @@ BN_PATHS = ("stats_pass", "stats_epilogue", "stats_split_inkernel", "fwd", "fwd_
 
 LAYOUT_XYTP_F64 = 0
 LAYOUT_DAT8 = 1
+EVT_20, EVT_21 = 20, 21   # the `encoding` argument of the frlw_evt2_* entry points
 TAF_U8_FLIP_K = 1
 
 _ERR_TEXT = {
@@ -170,6 +171,11 @@ SYMBOLS = {
     "frlw_evt3_count": (_I, [_P, _I64, _I, _I, _P, _P, _SZ, _P]),
     "frlw_evt3_emit": (_I, [_P, _I64, _I, _I, _P, _SZ, _P, _I64, _I, _P]),
     "frlw_evt3_result": (_I, [_P, _P, _P, _P, C.POINTER(C.c_int)]),
+    "frlw_evt2_workspace_bytes": (_SZ, [_I, _I64]),
+    "frlw_evt2_geometry": (_I, [_I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "frlw_evt2_count": (_I, [_I, _P, _I64, _I, _I, _P, _P, _SZ, _P]),
+    "frlw_evt2_emit": (_I, [_I, _P, _I64, _I, _I, _P, _SZ, _P, _I64, _I, _P]),
+    "frlw_evt2_result": (_I, [_P, _P, _P, _P, C.POINTER(C.c_int)]),
     "frlw_leaky_transform": (_I, [_P, _I64, _P, _P, _P]),
     "frlw_resize_nearest_f32": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "frlw_resize_nearest_u8": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),

@@ -500,6 +500,51 @@ int frlw_evt3_emit(const uint16_t *words, int64_t n_words, int width, int height
 int frlw_evt3_result(const void *workspace, frlw_stream_t stream, frlw_evt3_counters_t *counters, frlw_evt3_state_t *state_out,
                      int *status_out);
 
+/*
+ * Prophesee EVT 2.0 (32-bit words) and EVT 2.1 (64-bit words, 32 events a word) -> FRLW_LAYOUT_DAT8 records (csrc/evt2.hip), as
+ * DESIGN.md's "EVT 2.0 and EVT 2.1 decode" section defines the formats and tests/evt2_restated.py restates them.  The five entry
+ * points mirror the frlw_evt3_* five, with `encoding` in front: FRLW_EVT_20 or FRLW_EVT_21 (anything else: FRLW_ERR_ARG, 0 from the
+ * size query).  words: DEVICE, little-endian words of the encoding's width, aligned to that width (16-byte alignment is the fast
+ * case), at most 2^31 per call; width / height in 1..2048.  A longer stream is decoded piece by piece with the state carried; the
+ * cut may fall anywhere.
+ *
+ * frlw_evt2_count   enqueues four launches that leave plan, counters and carried-out state in the workspace.  state_in: HOST,
+ *                   NULL = start of stream.
+ * frlw_evt2_result  synchronises `stream` and copies counters (the record of the EVT 3.0 decoder: the same nine counters, min_t
+ *                   and max_t; t values unshifted), carried-out state (may be NULL) and the data-dependent status to the host:
+ *                   behind frlw_evt2_emit FRLW_ERR_SPAN a t does not fit 32 bits (or lies below the shift), FRLW_ERR_ARG
+ *                   capacity below counters.events -- NOTHING is written in either case; FRLW_ERR_HIP the words are not the ones
+ *                   counted.
+ * frlw_evt2_emit    one launch: the same encoding, words, n_words, width, height and workspace again; out: DEVICE, capacity
+ *                   records of 8 bytes, never written at or beyond capacity; time_shift != 0 subtracts (first EVT_TIME_HIGH of
+ *                   the stream) << 6 from every t.  Records come out in stream order (ascending bit inside an EVT 2.1 word), each
+ *                   written once.
+ * No kernel waits on another workgroup; no host synchronisation outside frlw_evt2_result.  frlw_evt2_workspace_bytes and
+ * frlw_evt2_geometry (words per workgroup chunk and per lane piece, per encoding) are HOST only; 0 = n_words negative or over the
+ * limit.  NULL pointers, a width or height outside 1..2048, a wrong struct_size: FRLW_ERR_ARG; a short workspace:
+ * FRLW_ERR_WORKSPACE; nothing is enqueued in either case.
+ */
+enum { FRLW_EVT_20 = 20, FRLW_EVT_21 = 21 };
+typedef struct frlw_evt2_state {
+    int32_t struct_size; /* sizeof(frlw_evt2_state_t) */
+    int32_t reserved;
+    uint32_t flags;      /* bit 0 EVT_TIME_HIGH seen */
+    uint32_t loops;      /* clock wraps so far */
+    uint32_t first_high; /* first EVT_TIME_HIGH of the stream */
+    uint32_t last_high;
+    uint32_t has_last_t; /* an event was emitted so far ... */
+    uint32_t reserved2;
+    uint64_t last_t;     /* ... and its t */
+} frlw_evt2_state_t;
+size_t frlw_evt2_workspace_bytes(int encoding, int64_t n_words);
+int frlw_evt2_geometry(int encoding, int *chunk_words, int *lane_words);
+int frlw_evt2_count(int encoding, const void *words, int64_t n_words, int width, int height, const frlw_evt2_state_t *state_in,
+                    void *workspace, size_t workspace_bytes, frlw_stream_t stream);
+int frlw_evt2_emit(int encoding, const void *words, int64_t n_words, int width, int height, void *workspace, size_t workspace_bytes,
+                   void *out, int64_t capacity, int time_shift, frlw_stream_t stream);
+int frlw_evt2_result(const void *workspace, frlw_stream_t stream, frlw_evt3_counters_t *counters, frlw_evt2_state_t *state_out,
+                     int *status_out);
+
 /* The verdict of the one-time LDS lane-order self-test of the fast paths (frlw_taf_encode_batch, frlw_ev_encode_batch, the
  * two-launch forms of frlw_sae_encode / frlw_eci_encode) for the CURRENT device: *ok_out = 1 when the property held, 0 when
  * it did not (those entry points then answer FRLW_ERR_UNSUPPORTED and callers take the general path -- same bits, different
