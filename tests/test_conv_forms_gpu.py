@@ -149,15 +149,21 @@ def operands(w, prec, H=0, W=0, stride=1):
     return wf, wd
 
 
-def run_fwd(x, w, stride, prec, scratch=True):
+def plain(name, shape, pitch):
+    """The allocator of run_fwd / run_dgrad / run_wgrad: a NaN-filled float32 tensor at exactly its size.  test_conv_edges_gpu.py
+    hands over one that puts every buffer between guard bands (name: for its messages; pitch: floats per row of the buffer)."""
+    return torch.full(shape, float("nan"), device="cuda")
+
+
+def run_fwd(x, w, stride, prec, scratch=True, alloc=plain):
     _, lib = _lib()
     B, H, W_, Cin = x.shape
     Cout, k = w.shape[0], w.shape[-1]
     pad = (k - 1) // 2
     Ho, Wo = (H + 2 * pad - k) // stride + 1, (W_ + 2 * pad - k) // stride + 1
     wf, _ = operands(w, prec)
-    z = torch.full((B, Ho, Wo, Cout), float("nan"), device="cuda")
-    sc = torch.full((SCRATCH,), float("nan"), device="cuda") if scratch else None
+    z = alloc("z", (B, Ho, Wo, Cout), Cout)
+    sc = alloc("split-K scratch", (SCRATCH,), (Cout + 31) // 32 * 32) if scratch else None
     torch.cuda.synchronize()
     before = counts()
     check_rc(lib.frlw_conv2d_fwd(ptr(x), B, H, W_, Cin, ptr(wf), Cout, k, stride, ptr(z), ptr(sc), SCRATCH if scratch else 0,
@@ -166,13 +172,13 @@ def run_fwd(x, w, stride, prec, scratch=True):
     return z, forms_moved(before)
 
 
-def run_dgrad(dz, w, stride, H, W, prec):
+def run_dgrad(dz, w, stride, H, W, prec, alloc=plain):
     _, lib = _lib()
     B, Ho, Wo, Cout = dz.shape
     Cin, k = w.shape[1], w.shape[-1]
     _, wd = operands(w, prec, H, W, stride)
-    dx = torch.full((B, H, W, Cin), float("nan"), device="cuda")
-    sc = torch.full((SCRATCH,), float("nan"), device="cuda")
+    dx = alloc("dx", (B, H, W, Cin), Cin)
+    sc = alloc("split-K scratch", (SCRATCH,), (Cin + 31) // 32 * 32)
     torch.cuda.synchronize()
     before = counts()
     check_rc(lib.frlw_conv2d_dgrad(ptr(dz), B, Ho, Wo, Cout, ptr(wd), Cin, k, stride, H, W, ptr(dx), ptr(sc), SCRATCH, prec, None),
@@ -181,14 +187,14 @@ def run_dgrad(dz, w, stride, H, W, prec):
     return dx, forms_moved(before)
 
 
-def run_wgrad(x, dz, k, stride, prec, scratch_part=1.0):
+def run_wgrad(x, dz, k, stride, prec, scratch_part=1.0, alloc=plain):
     _, lib = _lib()
     B, H, W, Cin = x.shape
     _, Ho, Wo, Cout = dz.shape
     want = lib.frlw_conv2d_wgrad_scratch_floats(B, Ho, Wo, Cin, Cout, k)
     n = int(want * scratch_part)
-    sc = torch.full((n,), float("nan"), device="cuda")
-    dw = torch.full((Cout, Cin, k, k), float("nan"), device="cuda")
+    sc = alloc("wgrad scratch", (n,), Cout)
+    dw = alloc("dw", (Cout, Cin, k, k), Cin * k * k)
     torch.cuda.synchronize()
     before = counts()
     check_rc(lib.frlw_conv2d_wgrad(ptr(x), B, H, W, Cin, ptr(dz), Ho, Wo, Cout, k, stride, ptr(dw), ptr(sc), n, prec, None),
