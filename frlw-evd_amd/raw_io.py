@@ -3,7 +3,8 @@ tests and tools.
 
 The formats as this project implements them are DESIGN.md's "EVT 3.0 decode" and "EVT 2.0 and EVT 2.1 decode" sections (written
 from the public descriptions; agreement with the vendor's decoder is unmeasured).  The decode runs on the GPU (csrc/evt3.hip through
-``frlw_evt3_count`` / ``frlw_evt3_emit``, csrc/evt2.hip through ``frlw_evt2_count`` / ``frlw_evt2_emit``) and returns what
+``frlw_evt3_count`` / ``frlw_evt3_emit``, csrc/evt2.hip through ``frlw_evt2_count`` / ``frlw_evt2_emit``, both on the plan of
+csrc/evt_plan.h) and returns what
 ``dat_io.DatFile.to_device`` returns: ``(n, 8)`` uint8 records, ``t:u32`` then ``x | y << 14 | p << 28``, so every encoder,
 ``StreamDetector`` and the renderer take a camera-native recording as they take a ``*_td.dat`` one.  There is no CPU decode here;
 ``encode_evt2`` / ``encode_evt21`` / ``encode_evt3`` / ``write_raw`` are host-only numpy.
@@ -287,29 +288,39 @@ class FrlwEvt3Counters(C.Structure):
         self.struct_size = C.sizeof(type(self))
 
 
-_ENC_ARG = {"EVT2": _lib.EVT_20, "EVT21": _lib.EVT_21}     # the `encoding` argument of the frlw_evt2_* entry points
-_WORD_BITS = {"EVT2": 32, "EVT21": 64, "EVT3": 16}
+class _Decoder:
+    """What the decode calls need to know about one encoding: the five ``<prefix>_*`` entry points, the ``encoding`` argument that
+    leads their arguments (EVT 2.x) or none (EVT 3.0), the state record and the width of a word."""
+
+    def __init__(self, name, prefix, lead, state, word_bits):
+        self.name, self.prefix, self.lead, self.state, self.word_bits = name, prefix, lead, state, word_bits
+
+    def call(self, what, *args):
+        entry = f"{self.prefix}_{what}"
+        return _lib.check(getattr(_lib.load(), entry)(*self.lead, *args), entry)
 
 
-def _enc_arg(encoding):
-    if encoding not in _ENC_ARG:
+_DECODERS = {"EVT2": _Decoder("EVT 2.0", "frlw_evt2", (_lib.EVT_20,), FrlwEvt2State, 32),
+             "EVT21": _Decoder("EVT 2.1", "frlw_evt2", (_lib.EVT_21,), FrlwEvt2State, 64),
+             "EVT3": _Decoder("EVT 3.0", "frlw_evt3", (), FrlwEvt3State, 16)}
+
+
+def _evt2_decoder(encoding):
+    if encoding not in ("EVT2", "EVT21"):
         raise ValueError(f"encoding: 'EVT2' or 'EVT21', not {encoding!r}")
-    return _ENC_ARG[encoding]
+    return _DECODERS[encoding]
 
 
 def geometry(encoding="EVT3"):
     """(words per workgroup chunk, words per lane piece) of the decode kernels of ``encoding``."""
     c, l = C.c_int(0), C.c_int(0)
-    if encoding == "EVT3":
-        _lib.check(_lib.load().frlw_evt3_geometry(C.byref(c), C.byref(l)), "frlw_evt3_geometry")
-    else:
-        _lib.check(_lib.load().frlw_evt2_geometry(_enc_arg(encoding), C.byref(c), C.byref(l)), "frlw_evt2_geometry")
+    (_DECODERS["EVT3"] if encoding == "EVT3" else _evt2_decoder(encoding)).call("geometry", C.byref(c), C.byref(l))
     return c.value, l.value
 
 
 def _words_on_device(words, encoding="EVT3"):
     import torch
-    bits = _WORD_BITS[encoding]
+    bits = _DECODERS[encoding].word_bits
     if not isinstance(words, torch.Tensor) or not words.is_cuda or words.dim() != 1 or not words.is_contiguous() \
             or words.element_size() * 8 != bits:
         raise ValueError(f"words: a contiguous 1-d {bits}-bit tensor on the GPU")
@@ -323,89 +334,68 @@ def _stream(t):
     return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
+def _result(d, workspace, words, state_out):
+    """-> (counters, the data-dependent status) behind the work enqueued on the stream of ``words``."""
+    counters, status = FrlwEvt3Counters(), C.c_int(0)
+    _lib.check(getattr(_lib.load(), d.prefix + "_result")(C.c_void_p(workspace.data_ptr()), _stream(words), C.byref(counters),
+                                                          None if state_out is None else C.byref(state_out), C.byref(status)),
+               d.prefix + "_result")
+    return counters, status.value
+
+
+def _count(words, size, state, encoding):
+    import torch
+    d = _DECODERS[encoding]
+    words = _words_on_device(words, encoding)
+    n = words.numel()
+    ws = torch.empty(getattr(_lib.load(), d.prefix + "_workspace_bytes")(*d.lead, n), dtype=torch.uint8, device=words.device)
+    d.call("count", C.c_void_p(words.data_ptr()), n, int(size[1]), int(size[0]), None if state is None else C.byref(state),
+           C.c_void_p(ws.data_ptr()), ws.numel(), _stream(words))
+    out = d.state()
+    return _result(d, ws, words, out)[0], out, ws
+
+
+def _emit(words, size, workspace, out, capacity, time_shift, encoding):
+    d = _DECODERS[encoding]
+    words = _words_on_device(words, encoding)
+    if out.numel() * out.element_size() < 8 * capacity:
+        raise ValueError("out is shorter than capacity records")
+    d.call("emit", C.c_void_p(words.data_ptr()), words.numel(), int(size[1]), int(size[0]), C.c_void_p(workspace.data_ptr()),
+           workspace.numel(), C.c_void_p(out.data_ptr()), int(capacity), 1 if time_shift else 0, _stream(words))
+    return _result(d, workspace, words, None)[1]
+
+
 def evt3_count(words, size, state=None):
     """The count call on ``words`` (GPU tensor of 16-bit words): -> ``(counters, state_out, workspace)``; ``counters`` a
     ``FrlwEvt3Counters`` (unshifted t), ``workspace`` the tensor that holds the plan ``evt3_emit`` needs."""
-    import torch
-    lib = _lib.load()
-    words = _words_on_device(words)
-    n = words.numel()
-    ws = torch.empty(lib.frlw_evt3_workspace_bytes(n), dtype=torch.uint8, device=words.device)
-    _lib.check(lib.frlw_evt3_count(C.c_void_p(words.data_ptr()), n, int(size[1]), int(size[0]),
-                                   None if state is None else C.byref(state), C.c_void_p(ws.data_ptr()), ws.numel(), _stream(words)),
-               "frlw_evt3_count")
-    counters, out = FrlwEvt3Counters(), FrlwEvt3State()
-    status = C.c_int(0)
-    _lib.check(lib.frlw_evt3_result(C.c_void_p(ws.data_ptr()), _stream(words), C.byref(counters), C.byref(out), C.byref(status)),
-               "frlw_evt3_result")
-    return counters, out, ws
+    return _count(words, size, state, "EVT3")
 
 
 def evt3_emit(words, size, workspace, out, capacity, time_shift=True):
     """The emit call: records to ``out`` (GPU uint8 tensor, at least ``8 * capacity`` bytes); -> the data-dependent status
     (``_lib.FRLW_OK``, ``FRLW_ERR_SPAN``: a t does not fit, ``FRLW_ERR_ARG``: capacity too small -- nothing is written then)."""
-    lib = _lib.load()
-    words = _words_on_device(words)
-    if out.numel() * out.element_size() < 8 * capacity:
-        raise ValueError("out is shorter than capacity records")
-    _lib.check(lib.frlw_evt3_emit(C.c_void_p(words.data_ptr()), words.numel(), int(size[1]), int(size[0]),
-                                  C.c_void_p(workspace.data_ptr()), workspace.numel(), C.c_void_p(out.data_ptr()), int(capacity),
-                                  1 if time_shift else 0, _stream(words)), "frlw_evt3_emit")
-    counters, status = FrlwEvt3Counters(), C.c_int(0)
-    _lib.check(lib.frlw_evt3_result(C.c_void_p(workspace.data_ptr()), _stream(words), C.byref(counters), None, C.byref(status)),
-               "frlw_evt3_result")
-    return status.value
+    return _emit(words, size, workspace, out, capacity, time_shift, "EVT3")
 
 
 def evt2_count(words, size, state=None, encoding="EVT2"):
     """``evt3_count`` for ``encoding`` 'EVT2' (32-bit words) or 'EVT21' (64-bit words): -> ``(counters, state_out, workspace)``;
     ``counters`` a ``FrlwEvt3Counters`` (unshifted t), ``state_out`` a ``FrlwEvt2State``."""
-    import torch
-    lib, enc = _lib.load(), _enc_arg(encoding)
-    words = _words_on_device(words, encoding)
-    n = words.numel()
-    ws = torch.empty(lib.frlw_evt2_workspace_bytes(enc, n), dtype=torch.uint8, device=words.device)
-    _lib.check(lib.frlw_evt2_count(enc, C.c_void_p(words.data_ptr()), n, int(size[1]), int(size[0]),
-                                   None if state is None else C.byref(state), C.c_void_p(ws.data_ptr()), ws.numel(), _stream(words)),
-               "frlw_evt2_count")
-    counters, out = FrlwEvt3Counters(), FrlwEvt2State()
-    status = C.c_int(0)
-    _lib.check(lib.frlw_evt2_result(C.c_void_p(ws.data_ptr()), _stream(words), C.byref(counters), C.byref(out), C.byref(status)),
-               "frlw_evt2_result")
-    return counters, out, ws
+    _evt2_decoder(encoding)
+    return _count(words, size, state, encoding)
 
 
 def evt2_emit(words, size, workspace, out, capacity, time_shift=True, encoding="EVT2"):
     """``evt3_emit`` for ``encoding`` 'EVT2' or 'EVT21': -> the data-dependent status (nothing is written unless it is
     ``_lib.FRLW_OK``)."""
-    lib, enc = _lib.load(), _enc_arg(encoding)
-    words = _words_on_device(words, encoding)
-    if out.numel() * out.element_size() < 8 * capacity:
-        raise ValueError("out is shorter than capacity records")
-    _lib.check(lib.frlw_evt2_emit(enc, C.c_void_p(words.data_ptr()), words.numel(), int(size[1]), int(size[0]),
-                                  C.c_void_p(workspace.data_ptr()), workspace.numel(), C.c_void_p(out.data_ptr()), int(capacity),
-                                  1 if time_shift else 0, _stream(words)), "frlw_evt2_emit")
-    counters, status = FrlwEvt3Counters(), C.c_int(0)
-    _lib.check(lib.frlw_evt2_result(C.c_void_p(workspace.data_ptr()), _stream(words), C.byref(counters), None, C.byref(status)),
-               "frlw_evt2_result")
-    return status.value
-
-
-def _count(words, size, state, encoding):
-    return evt3_count(words, size, state) if encoding == "EVT3" else evt2_count(words, size, state, encoding)
-
-
-def _emit(words, size, workspace, out, capacity, time_shift, encoding):
-    if encoding == "EVT3":
-        return evt3_emit(words, size, workspace, out, capacity, time_shift)
-    return evt2_emit(words, size, workspace, out, capacity, time_shift, encoding)
+    _evt2_decoder(encoding)
+    return _emit(words, size, workspace, out, capacity, time_shift, encoding)
 
 
 def _raise_for(status, encoding="EVT3"):
+    d = _DECODERS[encoding]
     if status == _lib.FRLW_ERR_SPAN:
-        name = {"EVT2": "EVT 2.0", "EVT21": "EVT 2.1", "EVT3": "EVT 3.0"}[encoding]
-        raise ValueError(f"{name} decode: recording longer than 2^32 us (a timestamp does not fit the 32 bits of a DAT record)")
-    _lib.check(status, "frlw_evt3_emit" if encoding == "EVT3" else "frlw_evt2_emit")
+        raise ValueError(f"{d.name} decode: recording longer than 2^32 us (a timestamp does not fit the 32 bits of a DAT record)")
+    _lib.check(status, d.prefix + "_emit")
 
 
 def _counters_dict(parts, shift):

@@ -454,7 +454,7 @@ int frlw_seq_nms(const float *boxes, const double *scores, const int32_t *labels
                  size_t workspace_bytes, frlw_stream_t stream);
 
 /*
- * Prophesee EVT 3.0 words -> FRLW_LAYOUT_DAT8 records (csrc/evt3.hip), as DESIGN.md's "EVT 3.0 decode" section defines the format
+ * Prophesee EVT 3.0 words -> FRLW_LAYOUT_DAT8 records (csrc/evt3.hip on csrc/evt_plan.h), as DESIGN.md's "EVT 3.0 decode" section defines the format
  * and tests/evt3_restated.py restates it.  words: DEVICE, little-endian 16-bit words (any 2-byte alignment; 16-byte alignment is
  * the fast case), at most 2^31 per call; width / height in 1..2048.  A longer stream is decoded piece by piece with the state
  * carried; the cut may fall anywhere, also inside a vector run.
@@ -501,7 +501,7 @@ int frlw_evt3_result(const void *workspace, frlw_stream_t stream, frlw_evt3_coun
                      int *status_out);
 
 /*
- * Prophesee EVT 2.0 (32-bit words) and EVT 2.1 (64-bit words, 32 events a word) -> FRLW_LAYOUT_DAT8 records (csrc/evt2.hip), as
+ * Prophesee EVT 2.0 (32-bit words) and EVT 2.1 (64-bit words, 32 events a word) -> FRLW_LAYOUT_DAT8 records (csrc/evt2.hip on csrc/evt_plan.h), as
  * DESIGN.md's "EVT 2.0 and EVT 2.1 decode" section defines the formats and tests/evt2_restated.py restates them.  The five entry
  * points mirror the frlw_evt3_* five, with `encoding` in front: FRLW_EVT_20 or FRLW_EVT_21 (anything else: FRLW_ERR_ARG, 0 from the
  * size query).  words: DEVICE, little-endian words of the encoding's width, aligned to that width (16-byte alignment is the fast

@@ -1,7 +1,7 @@
 """EVT 2.0 / EVT 2.1 decode on the GPU (csrc/evt2.hip through frlw_evd_amd.raw_io) against tests/evt2_restated.py: the output bytes,
 every counter and the carried state must be equal.  The streams put words on the real edges of the kernels' plan -- C words per
 workgroup chunk, L per lane piece, 64 L per wavefront (frlw_evt2_geometry, per encoding) -- and none is longer than three chunks and
-a few words."""
+a few words, but the one that gives the single-workgroup scans more chunks than they have threads."""
 import os
 import socket
 import subprocess
@@ -347,6 +347,16 @@ def test_fuzz(plan, seed):
         assert counters["events"] > 1000 and len(got) == counters["events"]
         for k in ("before_sync", "out_of_frame", "unsorted", "triggers", "other_words"):
             assert counters[k] > 0, k
+
+
+def test_more_chunks_than_scan_threads(plan):
+    """258 chunks and 17 words: each thread of the two single-workgroup scans has a range of two chunks, threads 0..129 have
+    work, the ranges of the rest are clipped to nothing."""
+    enc, C, L = plan
+    words = D.fuzz(258 * C + 17, 1100, enc)
+    assert -(-len(words) // C) > 256
+    _, counters = check(words, enc)
+    assert counters["events"] > 0 and counters["unsorted"] > 0 and counters["out_of_frame"] > 0
 
 
 # ---- the three encodings -----------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """EVT 3.0 decode on the GPU (csrc/evt3.hip through frlw_evd_amd.raw_io) against tests/evt3_restated.py: the output bytes and every
 counter must be equal.  The streams put words on the real edges of the kernels' plan -- C words per workgroup chunk, L per lane
-piece, 64 L per wavefront (frlw_evt3_geometry) -- and none is longer than about three chunks."""
+piece, 64 L per wavefront (frlw_evt3_geometry) -- and none is longer than about three chunks, but the one that gives the
+single-workgroup scans more chunks than they have threads."""
 import os
 import re
 import socket
@@ -227,6 +228,23 @@ def test_unaligned_words_pointer(geom):
     dat, counters, _ = raw_io.decode_evt3(dev.contiguous() if not dev.is_contiguous() else dev, SIZE)
     want, want_c, _ = R.decode(words, SIZE[1], SIZE[0])
     assert as_records(dat).tobytes() == want.tobytes() and counters == want_c
+
+
+def test_more_chunks_than_scan_threads(geom):
+    """258 chunks and 17 words: each thread of the two single-workgroup scans has a range of two chunks, threads 0..129 have
+    work, the ranges of the rest are clipped to nothing.  TIME_HIGH (rising, no wrap), TIME_LOW and ADDR_Y words spread over the
+    stream, so the state a range carries in differs from range to range."""
+    C, L = geom
+    n = 258 * C + 17
+    words = mixed(n, 91)
+    rng = np.random.default_rng(92)
+    at = np.sort(rng.choice(np.arange(8, n), size=900, replace=False))
+    highs = 7 + np.sort(rng.integers(0, 3000, size=300))
+    for i, pos in enumerate(at):
+        words[pos] = (D.th(int(highs[i // 3])), D.tl(int(rng.integers(0, 4096))), D.ay(int(rng.integers(0, 250))))[i % 3]
+    assert -(-n // C) > 256
+    _, counters = check(words)
+    assert counters["events"] > 0 and counters["unsorted"] > 0 and counters["out_of_frame"] > 0
 
 
 # ---- carried state -----------------------------------------------------------------------------------------------------------
