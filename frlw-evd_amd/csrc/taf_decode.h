@@ -22,6 +22,8 @@ struct FastGeom {
     int bin_shift, bin_mask; // direct mode (FastPlan): bin = tile << 4 | sub-tile of the cell; otherwise 0, 0: bin = tile
     int simple;   // the call meets the conditions of the SIMPLE decode (below): decided on the host
     uint32_t span; // n_windows * win when that fits 32 bits (SIMPLE)
+    int m24;      // SIMPLE and span < 2^24 and win_magic < 2^24 (win > 256): the window division of an in-span event fits the
+                  // full-rate 24-bit multiplies (simple_taf_fields_valid); decided on the host
     double rcp; // 1 / (win + 1e-8) (TAF) or 1 / win (Event Volume), IEEE f64, computed ONCE on the host: kf_hist checks that
                 // multiplying by it gives every r of the window the float the division gives; the tile kernels multiply
 };
@@ -75,23 +77,58 @@ __device__ __forceinline__ bool fast_alias(const FastGeom &G, int &x, int &y)
     return true;
 }
 
+// The two halves of the SIMPLE TAF decode that do not depend on where the event's time lies.
+// simple_cell: the cell inside the tile and the bin.  BINS = false: the caller knows bin_shift == 0 and bin_mask == 0 (tile bins).
+// (y >> thl < tiles_y and tiles_x are both at most kMaxFastTiles: the 24-bit multiply of the tile row is exact.)
+template <bool BINS = true>
+__device__ __forceinline__ uint32_t simple_cell(const FastGeom &G, uint32_t x, uint32_t y, uint32_t p, uint32_t &tile)
+{
+    const uint32_t tw1 = (1u << G.twl) - 1u, th1 = (1u << G.thl) - 1u;
+    const uint32_t cell = ((((y & th1) << G.twl) | (x & tw1)) << 1) | p;
+    tile = __umul24(y >> G.thl, (uint32_t)G.tiles_x) + (x >> G.twl);
+    if (BINS) tile = (tile << G.bin_shift) | ((cell >> 8) & (uint32_t)G.bin_mask);
+    return cell;
+}
+// simple_window: z = floor(relu / win) and the remainder, by a multiply-high and ONE correction step (floor(2^32 / win)
+// under-estimates the quotient by less than one).  M24: relu, win_magic and win are all below 2^24 (FastGeom::m24 and an
+// in-span event), so the high and the low 32 bits of the 48-bit products are what the full-rate 24-bit multiplies give.
+template <bool M24 = false>
+__device__ __forceinline__ uint32_t simple_window(const FastGeom &G, uint32_t relu, uint32_t &rem)
+{
+    uint32_t z = M24 ? __umulhi(relu & 0xffffffu, G.win_magic & 0xffffffu) : __umulhi(relu, G.win_magic); // floor(rel / win) or one less
+    uint32_t zw;
+    if (M24) asm("v_mul_u32_u24 %0, %1, %2" : "=v"(zw) : "s"(G.win), "v"(z)); // (__umul24 here comes out as the quarter-rate v_mul_lo_u32)
+    else zw = z * G.win;
+    rem = relu - zw;
+    if (rem >= G.win) { ++z; rem -= G.win; }
+    return z;
+}
+
 // The SIMPLE TAF fields of an in-frame event at time t: window, tile (bin) and record word.  false: t is outside
 // [t0, t0 + span] (ST_SPAN); the fields are computed either way, so a caller can select instead of branching (kf_scatter_cm).
-// (y >> thl < tiles_y and tiles_x are both at most kMaxFastTiles: the 24-bit multiply of the tile row is exact.)
+template <bool BINS = true>
 __device__ __forceinline__ bool simple_taf_fields(const FastGeom &G, int x, int y, uint32_t p, uint32_t t, uint32_t t0lo, uint32_t &tile,
                                                   uint32_t &word, uint32_t &window)
 {
     const uint32_t relu = t - t0lo;
-    uint32_t z = __umulhi(relu, G.win_magic); // floor(rel / win) or one less
-    uint32_t rem = relu - z * G.win;
-    if (rem >= G.win) { ++z; rem -= G.win; }
+    uint32_t rem, z = simple_window(G, relu, rem);
     if (z >= (uint32_t)G.n_windows) { z = (uint32_t)G.n_windows - 1u; rem = G.win; } // t == end of the last window
-    const uint32_t tw1 = (1u << G.twl) - 1u, th1 = (1u << G.thl) - 1u;
-    const uint32_t cell = (((((uint32_t)y & th1) << G.twl) | ((uint32_t)x & tw1)) << 1) | p;
-    tile = ((__umul24((uint32_t)y >> G.thl, (uint32_t)G.tiles_x) + ((uint32_t)x >> G.twl)) << G.bin_shift) | ((cell >> 8) & (uint32_t)G.bin_mask);
+    const uint32_t cell = simple_cell<BINS>(G, (uint32_t)x, (uint32_t)y, p, tile);
     window = z;
     word = (rem << (kCellBits + G.wb)) | (z << kCellBits) | cell;
     return !(t < t0lo || relu > G.span);
+}
+
+// The same fields of an event the caller KNOWS to be inside the frame and strictly inside the span (relu < span: the window
+// is below n_windows without the clamp), of a call with tile bins and FastGeom::m24 -- kf_scatter_cm's all-valid batches.
+__device__ __forceinline__ void simple_taf_fields_valid(const FastGeom &G, uint32_t x, uint32_t y, uint32_t p, uint32_t relu, uint32_t &tile,
+                                                        uint32_t &word, uint32_t &window)
+{
+    uint32_t rem;
+    const uint32_t z = simple_window<true>(G, relu, rem);
+    const uint32_t cell = simple_cell<false>(G, x, y, p, tile);
+    window = z;
+    word = (rem << (kCellBits + G.wb)) | (z << kCellBits) | cell;
 }
 
 template <bool HAS_MAP, bool EV = false, bool SIMPLE = false, int SAE = 0>

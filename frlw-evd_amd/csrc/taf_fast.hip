@@ -415,6 +415,7 @@ int taf_batch_run(int phases, const frlw_events_t *ev, const int64_t *seq_offset
     G.simple = (y_lo == 0 && H_full == H && window_us >= 2 &&
                 (unsigned long long)n_windows * (unsigned long long)window_us <= 0xffffffffull && t0_fits_simple(S)) ? 1 : 0;
     G.span = G.simple ? (uint32_t)((unsigned long long)n_windows * (unsigned long long)window_us) : 0u;
+    G.m24 = (G.simple && G.span < (1u << 24) && G.win_magic < (1u << 24)) ? 1 : 0;
 
     hipStream_t st = (hipStream_t)stream;
     char *w8 = (char *)workspace;

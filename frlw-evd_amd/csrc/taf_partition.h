@@ -493,10 +493,20 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(MAXB > kMax
     // LEAN: fast_decode<false, false, true>'s two helpers without its early returns -- every value is computed for every lane and
     // one mask `ok` decides, so the hot path has no nest of exec-mask branches with their default-value moves.  Same records,
     // flags and window masks as fast_decode.
+    // FASTBLK (LEAN, 20 batches: the headline's form, which never has direct bins -- taf_plan.h, `big`): a batch whose 64 lanes
+    // all hold an event inside the frame and strictly inside the span takes a block without any lane condition -- full EXEC, no
+    // error word, no `ok` / `live` selects, no clamp of the window (relu == span, the one valid case that needs it, goes the
+    // slow way with the errors), the window division in full-rate 24-bit multiplies, a 32-bit window mask.  One vote per batch
+    // decides, over compares the decode needs anyway; every other batch runs the LEAN code below as it was.  nfast: the run's
+    // full batches, or 0 where the call does not allow the block (FastGeom::m24; more than 32 windows; t0 + span past 2^32,
+    // where `relu >= span` alone would not see t < t0).  Same records, flags and window masks either way.
+    constexpr bool FASTBLK = LEAN && MAXB > kMaxBpw;
     uint32_t where[MAXB], word[MAXB];
     unsigned long long wseen = 0ull;
+    uint32_t wseen32 = 0u;
     int err = pre_err;
     const uint32_t t0lo = (uint32_t)t0;
+    const uint32_t nfast = FASTBLK && G.m24 && G.n_windows <= 32 && t0lo <= ~G.span ? nloc >> 6 : 0u;
 #pragma unroll
     for (int j = 0; j < MAXB; ++j) {
         where[j] = 0xffffffffu;
@@ -506,7 +516,22 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(MAXB > kMax
                 q[j + kAhead] = src[min((uint32_t)((j + kAhead) * kWave + lane), last)];
             asm volatile("" ::: "memory"); // (the request stays HERE: hoisted to the top it is the burst again)
         }
-        if (j < G.bpw) {
+        bool fast = false; // wave-uniform
+        uint32_t fx = 0u, fy = 0u, frel = 0u;
+        if (FASTBLK && (uint32_t)j < nfast) {
+            fx = q[j].y & 16383u; fy = (q[j].y >> 14) & 16383u; frel = q[j].x - t0lo;
+            // (three ballots, not one over the OR: the compiler then takes each compare's lane mask as it is)
+            fast = (__builtin_amdgcn_ballot_w64(fx >= (uint32_t)G.W) | __builtin_amdgcn_ballot_w64(fy >= (uint32_t)G.H_full) |
+                    __builtin_amdgcn_ballot_w64(frel >= G.span)) == 0ull;
+        }
+        if (fast) {
+            uint32_t tile, w, z;
+            simple_taf_fields_valid(G, fx, fy, (q[j].y >> 28) & 1u, frel, tile, w, z);
+            const uint32_t r = atomicAdd(&wcnt[tile], 1u);
+            wseen32 |= 1u << z;
+            word[j] = w;
+            where[j] = (tile << 16) | r;
+        } else if (j < G.bpw) {
             const uint32_t i = (uint32_t)(j * kWave + lane);
             if (LEAN) {
                 if (nloc > 0) { // wave-uniform: an empty run has loaded nothing
@@ -514,7 +539,7 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(MAXB > kMax
                     const uint32_t p = (q[j].y >> 28) & 1u;
                     const bool ib = !fast_alias(G, x, y);
                     uint32_t tile, w, z;
-                    const bool sb = !simple_taf_fields(G, x, y, p, q[j].x, t0lo, tile, w, z);
+                    const bool sb = !simple_taf_fields<!FASTBLK>(G, x, y, p, q[j].x, t0lo, tile, w, z);
                     const bool live = i < nloc, ok = live && !ib && !sb;
                     if (live && !ok) err |= ib ? ST_INDEX : ST_SPAN; // (no lane of a valid call)
                     uint32_t r = 0u;
@@ -538,6 +563,7 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(MAXB > kMax
             }
         }
     }
+    wseen |= wseen32;
     if (err) atomicOr(&serr, err);
     SPROF(2);
     __syncthreads();
