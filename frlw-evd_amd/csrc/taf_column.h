@@ -30,7 +30,7 @@ template <int NT>
 __device__ __forceinline__ uint32_t col_load(const CmP &m, const SeqTab &S, int s, int b, uint32_t *L, uint32_t *D, uint32_t *wsum)
 {
     constexpr int NWV = NT / kWave;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, wvs = __builtin_amdgcn_readfirstlane(wv);
     const int c0 = S.chunk0[s], C = S.chunk0[s + 1] - c0; // >= 1: an empty sequence keeps one (empty) chunk
     const uint32_t out0 = (uint32_t)(S.ev0[s] - S.ev0[0]);
     uint32_t carry = 0;
@@ -42,9 +42,13 @@ __device__ __forceinline__ uint32_t col_load(const CmP &m, const SeqTab &S, int 
         const uint32_t inc = wave_incl_scan(cnt);
         if (lane == kWave - 1) wsum[wv] = inc;
         __syncthreads();
-        uint32_t run = carry + inc - cnt, total = 0;
-#pragma unroll
-        for (int k = 0; k < NWV; ++k) { if (k < wv) run += wsum[k]; total += wsum[k]; }
+        // the wavefronts' sums, scanned by every wavefront for itself with lane k = wavefront k: the sum of the wavefronts in front
+        // of this one and the pass's total come out of two lanes as SCALARS.  (As "for k: if (k < wv) run += wsum[k]" the compiler
+        // kept the NWV - 1 lane masks of `k < wv` in scalar register pairs across the pass: 30 of them in a 1024-thread kernel,
+        // which pushed kf_split_whole<true>'s list pointers out into a vector register -- the one its gather then spilled a record for.)
+        const uint32_t ws = lane < NWV ? wsum[lane] : 0u, wsi = wave_incl_scan(ws);
+        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)wsi, NWV - 1);
+        const uint32_t run = carry + inc - cnt + (uint32_t)__builtin_amdgcn_readlane((int)(wsi - ws), wvs);
         if (c < C) {
             L[c] = run;
             D[c] = out0 + (uint32_t)c * (uint32_t)m.chunk_ev + (e & 0xffffu) - run;

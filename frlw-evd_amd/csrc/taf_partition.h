@@ -381,7 +381,13 @@ __global__ __launch_bounds__(kFT) void kf_scatter(FastGeom G, SeqTab S, const ui
 #ifndef FRLW_SCATTER_AHEAD
 #define FRLW_SCATTER_AHEAD 4
 #endif
-#if defined(FRLW_WALK_PROF) || defined(FRLW_SCAT_PROF) // developer timeline of kf_taf_walk / kf_scatter_cm (tools/enc_lab.cpp prints it): cycles between stamps, summed over workgroups
+// (-DFRLW_SPLIT_PROF, the timeline of kf_split_whole<true>: the reader of the sums, frlw_debug_walk_prof in taf_fast.hip, is compiled for
+// the two older names; a build with the split's name alone borrows the scatter's, with the scatter's own stamps left out)
+#if defined(FRLW_SPLIT_PROF) && !defined(FRLW_WALK_PROF) && !defined(FRLW_SCAT_PROF)
+#define FRLW_SCAT_PROF
+#define FRLW_SCAT_PROF_READER_ONLY
+#endif
+#if defined(FRLW_WALK_PROF) || defined(FRLW_SCAT_PROF) // developer timeline of kf_taf_walk / kf_scatter_cm / kf_split_whole<true> (tools/enc_lab.cpp prints it): cycles between stamps, summed over workgroups
 constexpr int kProfWgs = 131072;
 __device__ unsigned long long g_walk_prof[kProfWgs * 9];
 #define XPROF(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); pd_[i] += t_ - tp_; tp_ = t_; } while (0)
@@ -397,7 +403,7 @@ __device__ unsigned long long g_walk_prof[kProfWgs * 9];
 #define WPROF_INIT() do { } while (0)
 #define WPROF_END() do { } while (0)
 #endif
-#ifdef FRLW_SCAT_PROF
+#if defined(FRLW_SCAT_PROF) && !defined(FRLW_SCAT_PROF_READER_ONLY)
 #define SPROF(i) XPROF(i)
 #define SPROF_INIT() XPROF_INIT()
 #define SPROF_END() XPROF_END()
@@ -407,6 +413,23 @@ __device__ unsigned long long g_walk_prof[kProfWgs * 9];
 #define SPROF_INIT() do { } while (0)
 #define SPROF_END() do { } while (0)
 #define SPROF_DRAIN() do { } while (0)
+#endif
+// kf_split_whole<true> (taf_split.h), stamps of thread 0's wavefront: 0 column loaded | 1 cursor value in hand | 2 barrier in front of
+// the gather passed | 3 last gather load issued | 4 tickets done | 5 prefixes done | 6, 7 the two barriers of every staging chunk
+// (summed over the chunks) | 8 end.  PPROF_CURSOR(n) waits for thread 0's returning add and for nothing younger: its wavefront has
+// issued eight loads per staging chunk behind it, and loads and returning adds come back in the order they were issued.
+#ifdef FRLW_SPLIT_PROF
+#define PPROF(i) XPROF(i)
+#define PPROF_INIT() XPROF_INIT()
+#define PPROF_END() XPROF_END()
+#define PPROF_CURSOR(n) do { /* s_waitcnt vmcnt(8 | 16 | 24 | 32), the other counters untouched */ \
+        if ((n) <= 8192u) __builtin_amdgcn_s_waitcnt(0x0F78); else if ((n) <= 16384u) __builtin_amdgcn_s_waitcnt(0x4F70); \
+        else if ((n) <= 24576u) __builtin_amdgcn_s_waitcnt(0x4F78); else __builtin_amdgcn_s_waitcnt(0x8F70); } while (0)
+#else
+#define PPROF(i) do { } while (0)
+#define PPROF_INIT() do { } while (0)
+#define PPROF_END() do { } while (0)
+#define PPROF_CURSOR(n) do { } while (0)
 #endif
 template <bool HAS_MAP, bool EV = false, bool SIMPLE = false, int MAXB = kMaxBpw, int SAE = 0>
 __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(MAXB > kMaxBpw ? 4 : 8, MAXB > kMaxBpw ? 4 : 8))) void kf_scatter_cm(FastGeom G, SeqTab S, uint32_t *dir, uint32_t *records, FastHeader *hdr, float *tlut_w,

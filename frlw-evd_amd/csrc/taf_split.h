@@ -86,6 +86,19 @@ __device__ __forceinline__ void split_count_segment(const TileP &q, uint32_t seg
     }
 }
 
+// Inclusive prefix sums inside every row of 16 lanes (lane & 15 = sub-tile), in registers: the first four steps of wave_incl_scan.
+// (As four __shfl_up + compare steps the compiler kept the four shuffle addresses in vector registers from the first scan to the
+// last chunk's, and every step was a trip through LDS.)  All lanes must be active.
+__device__ __forceinline__ uint32_t row16_incl_scan(uint32_t v)
+{
+    static_assert(kFW == 16, "one DPP row per set of sub-tile counters");
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false); // row_shr:1
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false); // row_shr:2
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false); // row_shr:4
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false); // row_shr:8
+    return v;
+}
+
 // 4a. Tiles of ordinary size (at most kSplitWhole records): ONE workgroup per (sequence, tile) reorders the tile's
 // records sub-tile-major, STABLY, in ONE pass over the list: every thread loads its (up to) 32 records at once -- all
 // loads of the tile in flight together, the list is read once and stays in registers -- and takes one returning LDS
@@ -139,7 +152,8 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     // chunk's stretch of rec[] (a run is ~43 records at an arbitrary offset on the headline: 2.3 lines for 1.3 lines' worth of
     // records), and neighbouring BLOCKS sit on different L2s.  Everything below is keyed by g, never by the block.
     const int g = CM ? (int)xcd_owned_index(blockIdx.x, gridDim.x) : blk;
-    uint32_t beg, n;
+    PPROF_INIT(); // (developer timeline, -DFRLW_SPLIT_PROF: the stamps are listed in taf_partition.h)
+    uint32_t beg = 0u, n;
     uint32_t m[kWholeChunks][RPT];
     if (CM) {
         const int s = g / q.T, C = S.chunk0[s + 1] - S.chunk0[s];
@@ -155,6 +169,7 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         // they turned every "is this chunk of the list there at all" test below into divergent control flow, and 19 of the 32
         // records were spilled)
         n = col_load<kFT>(cm, S, s, g - s * q.T, colL, colD, &wtot[0][0]);
+        PPROF(0);
         if (status0 != 0) return;
         if (n == 0u) {
             if (tid < kFW) { q.sub[(long long)g * kFW + tid] = 0u; q.sub_end[(long long)g * kFW + tid] = 0u; }
@@ -162,10 +177,23 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             return;
         }
         const bool hot = n > q.tile_max;
+        // The tile's 16 lists: n records of rec2[] from `start` on.  The add is ISSUED here, so that its trip to the header overlaps
+        // the table build and the gather, but an ordinary tile does not wait for it here: every workgroup of the launch books on this
+        // one word at about the same moment (they queue there), and a wait in front of the barrier below kept the other fifteen
+        // wavefronts -- and the tile's gather -- behind thread 0's place in that queue.  The value stays in thread 0's register
+        // until the last gather address is out and is published by the barrier behind the tickets.
+        uint32_t start = 0u;
         if (tid == 0) {
-            s_start = atomicAdd(&q.hdr->rec_cursor, n); // the tile's 16 lists: n records of rec2[] from here
-            if (hot) s_first = atomicAdd(&q.hdr->seg_cursor, (n + kSplitSeg - 1) / kSplitSeg);
-            if (q.wst && hot) q.wst_flag[g] = 0u; // (the segment kernels place this tile: no table)
+            // (an offset of zero through a vector register: with a uniform address the compiler folds the add over the wavefront's
+            // active lanes and reads the sum back with a readfirstlane right here -- which is a wait for the returning add, right here)
+            uint32_t zero = 0u;
+            asm volatile("" : "+v"(zero));
+            start = atomicAdd(&q.hdr->rec_cursor + zero, n);
+            if (hot) { // (needs both values at once: the wait stays here)
+                s_start = start;
+                s_first = atomicAdd(&q.hdr->seg_cursor, (n + kSplitSeg - 1) / kSplitSeg);
+                if (q.wst) q.wst_flag[g] = 0u; // (the segment kernels place this tile: no table)
+            }
             s_unsorted = 0;
         }
         if (q.wst && !hot) { // the tile's rows of the window table start at "no record" (published by the barriers below)
@@ -186,6 +214,7 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             col_index<kFT>(colL, C, 0u, n, idx);
         }
         __syncthreads();
+        PPROF(2);
         const uint32_t wvs = (uint32_t)__builtin_amdgcn_readfirstlane(wv); // (the wavefront index as a scalar: uniform branches below)
         // 1. the whole list into registers: list position -> address through the block table (without one: chunk through the index + a
         // walk over at most a few run boundaries); the loads go through one buffer descriptor with 32-bit offsets: with 64-bit
@@ -248,9 +277,22 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                     m[c][u] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)(off << 2), 0, 0);
                 }
             }
+            // This form's records are waited for HERE (s_waitcnt vmcnt(0)), not by its tickets.  Both forms hold divergent loops, so
+            // the compiler chains them -- this one, then the table form, each skipped by a flag -- and places its waits for a register
+            // as if a workgroup could run both: the table form's first loads waited for loads only THIS form issues into the same
+            // registers -- in effect for everything their wavefront had in flight: three of its first four records (one memory round
+            // trip in every gather) and thread 0's returning add.  Drained here, this form leaves nothing to wait for.  Its own
+            // tickets lose next to nothing: the first of them waited for all but seven of the records anyway.
+            __builtin_amdgcn_s_waitcnt(0x0F70); // (vmcnt(0), expcnt and lgkmcnt left alone)
             }
         }
-        beg = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_start);
+        // The last gather address is out: thread 0's wavefront waits for the add here, the other fifteen do not -- and they all wait
+        // for their records next, which were requested behind the add and come back behind it.  (The empty asm: the compiler waits
+        // for a value where it is first used, and would move this store up to the add.)
+        PPROF(3);
+        PPROF_CURSOR(n);
+        PPROF(1);
+        if (tid == 0) { asm volatile("" : "+v"(start)); s_start = start; }
         // (the column is dead once the last address is out; its space is written again in step 4, three barriers from here)
     } else {
         beg = q.base[g];
@@ -292,6 +334,7 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             }
         }
     }
+    if (CM) PPROF(4);
     __syncthreads();
     // 3. wavefront b: exclusive prefix of sub-tile b's batch counts in stream order (eight scans of 64 batches)
     {
@@ -308,15 +351,12 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         if (lane == 0) vtot[wv] = carry;
     }
     __syncthreads();
+    if (CM) PPROF(5);
+    if (CM) beg = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_start); // (published two barriers ago, behind the tickets)
     {
         // every wavefront: where the 16 lists start (its own copy: no further barrier)
         const uint32_t t = vtot[lane & 15];
-        uint32_t inc = t;
-#pragma unroll
-        for (int o2 = 1; o2 < kFW; o2 <<= 1) {
-            const uint32_t u = __shfl_up(inc, o2);
-            if ((lane & 15) >= o2) inc += u;
-        }
+        const uint32_t inc = row16_incl_scan(t);
         if (lane < kFW) {
             vbeg[wv][lane] = beg + inc - t;
             if (wv == 0) {
@@ -343,12 +383,7 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             const uint32_t p0 = scnt[b * kWholeRow + c * (kSplitSeg / kWave)];
             const uint32_t p1 = (uint32_t)((c + 1) * kSplitSeg) < n ? scnt[b * kWholeRow + (c + 1) * (kSplitSeg / kWave)] : vtot[b];
             const uint32_t cnt = p1 - p0;
-            uint32_t inc = cnt;
-#pragma unroll
-            for (int o2 = 1; o2 < kFW; o2 <<= 1) {
-                const uint32_t u = __shfl_up(inc, o2);
-                if (b >= o2) inc += u;
-            }
+            const uint32_t inc = row16_incl_scan(cnt);
             if (lane < kFW) {
                 cE[wv][lane] = (inc - cnt) - p0;
                 cD[wv][lane] = vbeg[wv][lane] + p0 - (inc - cnt);
@@ -365,6 +400,7 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             }
         }
         __syncthreads();
+        if (CM) PPROF(6);
         // (CM, TAF) the window starts kf_taf_walk needs, so that it does not have to scan its list for them.  The staged chunk is
         // sub-tile-major and stable: neighbours of one sub-tile are neighbours of that sub-tile's LIST.  A record whose sub-tile or
         // window differs from its staged predecessor's (and the chunk's first record) is a candidate for "first record of its
@@ -418,6 +454,7 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         // barrier there (a __syncthreads() would make the workgroup wait for the drain of its last 32 KB of stores)
         if (wtab && (uint32_t)((c + 1) * kSplitSeg) >= n) LDS_BARRIER();
         else __syncthreads();
+        if (CM) PPROF(7);
     }
     // 5. (CM, TAF) a window index that DEcreases between list neighbours marks the tile unsorted (the walk then filters the whole
     // list per window, as it does after its own scan): inside a chunk the sweep saw it at the neighbour; across chunks it is the
@@ -433,6 +470,7 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         LDS_BARRIER();
         if (tid == 0) q.wst_flag[g] = s_unsorted ? 2u : 1u;
     }
+    if (CM) { PPROF(8); PPROF_END(); }
 }
 
 // 4b. Skewed tiles (more than kSplitWhole records).  Reorders every tile's records sub-tile-major (sub-tile = the 256 cells [256 v, 256 v + 256) one workgroup of
