@@ -26,46 +26,83 @@ import torch
 
 from . import _lib
 
-_WORKSPACES = {}
+_WORKSPACES = {}  # (slot, device index, stream) -> uint8 tensor: one per kind of call, see _slot_workspace
 TUNING = None  # a _lib.FrlwTuning to attach to every encoder call (experiments / tests forcing a path); None = defaults
 FAST_MIN_EVENTS = 1_000_000  # single streams shorter than this take the general TAF path (encode_taf_dat, fast="auto")
 # False: every encoder takes the general path (the batched entry points raise NotImplementedError like on a device that failed the
 # lane-order self-test).  Set by dist.agree_fast_path() when ANY rank of the job failed it: results do not depend on the path,
 # step times do, and ranks that wait for each other in a collective should not run different kernels.
 FAST_PATH_ENABLED = True
+_FAST_PATH_OFF = "the fast path is switched off for this job (dist.agree_fast_path: a rank failed the self-test)"
+_MAX_WINDOWS = 64  # windows one TAF launch takes: longer labels / chains run in groups (_group_cuts)
+_GENERAL = object()  # _fast_or_general's answer "run the general path"
+
+
+def _stream_id():
+    """``torch.cuda.current_stream().cuda_stream``.  Asked with the device index: torch resolves an explicit index in half the time
+    it takes to resolve a missing one (1.3 against 2.6 us), and every call here asks at least twice."""
+    return torch.cuda.current_stream(torch.cuda.current_device()).cuda_stream
 
 
 def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    return C.c_void_p(_stream_id())
 
 
-def _workspace(n, H, W, device):
-    lib = _lib.load()
-    need = lib.frlw_encoder_workspace_bytes(int(n), int(H), int(W))
-    if need == 0:
-        raise ValueError(f"unsupported encode shape {H}x{W}")
-    key = (device.index, torch.cuda.current_stream().cuda_stream)
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _records(dat):
+    return dat.numel() * dat.element_size() // 8
+
+
+# ------------------------------------------------------------------------------------------------
+# workspaces and their deferred status
+# ------------------------------------------------------------------------------------------------
+def _slot_workspace(need, device, slot):
+    """The workspace of ``slot`` on the current stream, grown to ``need`` bytes.  A fresh one gets a zeroed header
+    (``frlw_workspace_init``): the deferred status word starts clean.  An outgrown one hands over what it has accumulated first."""
+    key = (slot, device.index, _stream_id())
     ws = _WORKSPACES.get(key)
     if ws is None or ws.numel() < need:
-        ws = _new_workspace(ws, need, device)
+        if ws is not None:
+            _finish(ws, "encoder call (workspace outgrown)")
+        ws = torch.empty(int(need * 1.25) + 4096, dtype=torch.uint8, device=device)
+        _lib.check(_lib.load().frlw_workspace_init(_ptr(ws), ws.numel(), _stream()), "frlw_workspace_init")
         _WORKSPACES[key] = ws
     return ws
 
 
-def _new_workspace(old, need, device):
-    """A fresh workspace with a zeroed header (``frlw_workspace_init``): the deferred status word starts clean.  An
-    outgrown workspace hands over what it has accumulated first."""
-    if old is not None:
-        _raise_deferred_of(old, "encoder call (workspace outgrown)")
-    ws = torch.empty(int(need * 1.25) + 4096, dtype=torch.uint8, device=device)
-    _lib.check(_lib.load().frlw_workspace_init(C.c_void_p(ws.data_ptr()), ws.numel(), _stream()), "frlw_workspace_init")
-    return ws
+def _workspace(n, H, W, device):
+    """The general path's workspace (csrc/encoders.hip)."""
+    need = _lib.load().frlw_encoder_workspace_bytes(int(n), int(H), int(W))
+    if need == 0:
+        raise ValueError(f"unsupported encode shape {H}x{W}")
+    return _slot_workspace(need, device, "general")
 
 
-def _raise_deferred_of(ws, what):
+def _batch_workspace(n, n_seq, H, W, window_us, device, slot="batch"):
+    """The fast path's workspace (csrc/taf_fast.hip); None = the shape / window is outside that path."""
+    need = _lib.load().frlw_taf_batch_workspace_bytes(int(n), int(n_seq), int(H), int(W), int(window_us))
+    return _slot_workspace(need, device, slot) if need else None
+
+
+def _finish(ws, what):
+    """Synchronise and surface data-dependent errors the way torch would (IndexError): the status of this call and of any
+    unchecked call on the same workspace before it, read and cleared in one go (``frlw_encoder_deferred_status``)."""
     st = C.c_int(0)
-    _lib.check(_lib.load().frlw_encoder_deferred_status(C.c_void_p(ws.data_ptr()), _stream(), C.byref(st)), what)
+    _lib.check(_lib.load().frlw_encoder_deferred_status(_ptr(ws), _stream(), C.byref(st)), what)
     _lib.check(st.value, what)
+
+
+def _run(rc, what, ws, check, unsupported=None):
+    """The tail of every library call: ``rc`` is what it returned.  ``unsupported``: the call may turn its input down
+    (``FRLW_ERR_UNSUPPORTED``), which raises ``NotImplementedError`` with that text."""
+    if unsupported is not None and rc == _lib.FRLW_ERR_UNSUPPORTED:
+        raise NotImplementedError(unsupported)
+    _lib.check(rc, what)
+    if check:
+        _finish(ws, what)
 
 
 def raise_deferred(what="encoder calls since the last check"):
@@ -73,14 +110,10 @@ def raise_deferred(what="encoder calls since the last check"):
     encoder call made on the current stream since the last check (IndexError / ValueError like the checked calls).  An
     unchecked fast-path call whose events leave the sequence span or the frame writes nothing -- call this before
     trusting its state / outputs (``e2e.SyntheticTafSource.encode_u8`` does, once per batch)."""
-    stream = torch.cuda.current_stream().cuda_stream
+    stream = _stream_id()
     for key, ws in list(_WORKSPACES.items()):
         if key[-1] == stream and ws.device.index == torch.cuda.current_device():
-            _raise_deferred_of(ws, what)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
+            _finish(ws, what)
 
 
 def fast_path_ok(device=None):
@@ -94,6 +127,9 @@ def fast_path_ok(device=None):
     return bool(ok.value)
 
 
+# ------------------------------------------------------------------------------------------------
+# arguments: every per-sequence argument is length-checked here, before the library sees it
+# ------------------------------------------------------------------------------------------------
 def _events_f64(events):
     if not events.is_cuda:
         raise RuntimeError("events must be a CUDA (ROCm) tensor: this path has no CPU implementation")
@@ -124,10 +160,52 @@ def _events_dat(dat, xmap=None, ymap=None):
                               C.pointer(TUNING) if TUNING is not None else None)
 
 
-def _finish(ws, what):
-    """Synchronise and surface data-dependent errors the way torch would (IndexError): the status of this call and of any
-    unchecked call on the same workspace before it, read and cleared in one go (``frlw_encoder_deferred_status``)."""
-    _raise_deferred_of(ws, what)
+def _sequences(seq_offsets, n):
+    """``(offs, B)`` of a sequence list over ``n`` records: sequence ``s`` owns the records ``[offs[s], offs[s + 1])``."""
+    offs = [int(o) for o in seq_offsets]
+    B = len(offs) - 1
+    if B < 1 or B > _lib.MAX_SEQUENCES:
+        raise ValueError(f"1..{_lib.MAX_SEQUENCES} sequences per call")
+    if offs[0] < 0 or offs[-1] > n or offs != sorted(offs):
+        raise ValueError(f"seq_offsets must ascend inside 0..{n}")
+    return offs, B
+
+
+def _ranges(ranges, n, what=None):
+    """The record ranges ``(lo, hi)`` as a list of int pairs inside ``n`` records.  ``what`` names them ("windows", "steps") for a
+    call that takes 1..64 of them; None: any number (the caller cuts the list into calls itself)."""
+    rng = [(int(lo), int(hi)) for lo, hi in ranges]
+    if what is not None and not 1 <= len(rng) <= _lib.MAX_SEQUENCES:
+        raise ValueError(f"1..{_lib.MAX_SEQUENCES} {what} per call")
+    for lo, hi in rng:
+        if lo < 0 or hi < lo or hi > n:
+            raise ValueError(f"record range ({lo}, {hi}) outside 0 <= lo <= hi <= {n}")
+    return rng
+
+
+def _per_item(value, B, name):
+    """One int per sequence / window: an int applies to all, a list must hold exactly ``B`` (ctypes would zero-fill a shorter
+    one without a word and raise IndexError, which here means "event coordinate out of range", for a longer one)."""
+    if not hasattr(value, "__len__"):
+        return [int(value)] * B
+    items = [int(v) for v in value]
+    if len(items) != B:
+        raise ValueError(f"one `{name}` per sequence / window: {len(items)} for {B}")
+    return items
+
+
+def _lamdas(lamdas):
+    """``(c_double array, L)``; the array is at least one long so that the library always gets a pointer."""
+    L = len(lamdas)
+    if L > _lib.MAX_LAMDAS:
+        raise ValueError(f"at most {_lib.MAX_LAMDAS} lamdas")
+    return (C.c_double * max(L, 1))(*[float(l) for l in lamdas]), L
+
+
+def _outputs(shape, device, want_f32, want_u8, u8_shape=None):
+    """``(f32 or None, u8 or None)``: the uninitialised output pair of a call (``u8_shape``: where the two differ)."""
+    return (torch.empty(shape, dtype=torch.float32, device=device) if want_f32 else None,
+            torch.empty(u8_shape or shape, dtype=torch.uint8, device=device) if want_u8 else None)
 
 
 def coordinate_maps(sensor_shape, shape, device):
@@ -150,9 +228,8 @@ def generate_eventframe(events, shape):
     ev, desc = _events_f64(events)
     out = torch.empty((2, H, W), dtype=torch.float32, device=ev.device)
     ws = _workspace(ev.shape[0], H, W, ev.device)
-    _lib.check(_lib.load().frlw_eci_encode(C.byref(desc), H, W, _ptr(out), None, _ptr(ws), ws.numel(), _stream()),
-               "generate_eventframe")
-    _finish(ws, "generate_eventframe")
+    _run(_lib.load().frlw_eci_encode(C.byref(desc), H, W, _ptr(out), None, _ptr(ws), ws.numel(), _stream()),
+         "generate_eventframe", ws, True)
     return out, time.time() - tick
 
 
@@ -163,9 +240,8 @@ def generate_agile_event_volume_cuda(events, shape, events_window=50000, volume_
     ev, desc = _events_f64(events)
     out = torch.empty((2 * volume_bins, H, W), dtype=torch.float32, device=ev.device)
     ws = _workspace(ev.shape[0], H, W, ev.device)
-    _lib.check(_lib.load().frlw_ev_encode(C.byref(desc), H, W, int(volume_bins), 0, 1, _ptr(out), None, _ptr(ws),
-                                          ws.numel(), _stream()), "generate_agile_event_volume_cuda")
-    _finish(ws, "generate_agile_event_volume_cuda")
+    _run(_lib.load().frlw_ev_encode(C.byref(desc), H, W, int(volume_bins), 0, 1, _ptr(out), None, _ptr(ws), ws.numel(), _stream()),
+         "generate_agile_event_volume_cuda", ws, True)
     return out, time.time() - tick
 
 
@@ -174,15 +250,13 @@ def generate_leaky_cuda(events, shape, lamdas, memory, now):
     tick = time.time()
     H, W = int(shape[0]), int(shape[1])
     ev, desc = _events_f64(events)
-    lam = (C.c_double * len(lamdas))(*[float(l) for l in lamdas])
-    out = torch.empty((2 * len(lamdas), H, W), dtype=torch.float32, device=ev.device)
+    lam, L = _lamdas(lamdas)
+    out = torch.empty((2 * L, H, W), dtype=torch.float32, device=ev.device)
     mem_out = torch.empty((2, H, W), dtype=torch.float32, device=ev.device)
     mem_in = None if memory is None else memory.to(torch.float32).contiguous()
     ws = _workspace(ev.shape[0], H, W, ev.device)
-    _lib.check(_lib.load().frlw_sae_encode(C.byref(desc), H, W, lam, len(lamdas), _ptr(mem_in), _ptr(mem_out),
-                                           int(now), 0, _ptr(out), None, _ptr(ws), ws.numel(), _stream()),
-               "generate_leaky_cuda")
-    _finish(ws, "generate_leaky_cuda")
+    _run(_lib.load().frlw_sae_encode(C.byref(desc), H, W, lam, L, _ptr(mem_in), _ptr(mem_out), int(now), 0, _ptr(out), None,
+                                     _ptr(ws), ws.numel(), _stream()), "generate_leaky_cuda", ws, True)
     return out, mem_out, time.time() - tick
 
 
@@ -211,9 +285,8 @@ def generate_taf_cuda(events, shape, past_volume=None, volume_bins=5):
         state = past_volume.to(torch.float32).contiguous().clone()
     view = torch.empty((2 * K, H, W), dtype=torch.float32, device=ev.device)
     ws = _workspace(ev.shape[0], H, W, ev.device)
-    _lib.check(_lib.load().frlw_taf_encode(C.byref(desc), H, W, K, 0, 1, 1, _ptr(state), _ptr(view), None, 0,
-                                           _ptr(ws), ws.numel(), _stream()), "generate_taf_cuda")
-    _finish(ws, "generate_taf_cuda")
+    _run(_lib.load().frlw_taf_encode(C.byref(desc), H, W, K, 0, 1, 1, _ptr(state), _ptr(view), None, 0, _ptr(ws), ws.numel(),
+                                     _stream()), "generate_taf_cuda", ws, True)
     return view, state, time.time() - tick
 
 
@@ -228,12 +301,12 @@ def leaky_transform(ecd):
 def resize_nearest(volume, target_shape):
     """``F.interpolate(volume[None], size=target_shape, mode='nearest')[0]`` (generate_eventvolume.py:149)."""
     src = volume.contiguous()
+    if src.dtype not in (torch.uint8, torch.float32):
+        raise ValueError("resize_nearest: float32 or uint8")
     Cn, H, W = src.shape
     Ho, Wo = int(target_shape[0]), int(target_shape[1])
     out = torch.empty((Cn, Ho, Wo), dtype=src.dtype, device=src.device)
     fn = _lib.load().frlw_resize_nearest_u8 if src.dtype == torch.uint8 else _lib.load().frlw_resize_nearest_f32
-    if src.dtype not in (torch.uint8, torch.float32):
-        raise ValueError("resize_nearest: float32 or uint8")
     _lib.check(fn(_ptr(src), Cn, H, W, Ho, Wo, _ptr(out), _stream()), "resize_nearest")
     return out
 
@@ -250,18 +323,6 @@ def quantize_u8(volume, clip255=False):
 # ------------------------------------------------------------------------------------------------
 # fused DAT-record fast path (harness glue on device)
 # ------------------------------------------------------------------------------------------------
-def _batch_workspace(n, n_seq, H, W, window_us, device, slot="batch"):
-    need = _lib.load().frlw_taf_batch_workspace_bytes(int(n), int(n_seq), int(H), int(W), int(window_us))
-    if need == 0:
-        return None
-    key = (slot, device.index, torch.cuda.current_stream().cuda_stream)
-    ws = _WORKSPACES.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _new_workspace(ws, need, device)
-        _WORKSPACES[key] = ws
-    return ws
-
-
 def encode_taf_batch(dat, seq_offsets, shape, state, t_start, window_us=10000, n_windows=8, volume_bins=8,
                      want_view=False, want_u8=True, flip_k=True, xmap=None, ymap=None, check=True):
     """The harness loop generate_taf.py:193-235 for a batch of independent sequences in one launch sequence
@@ -280,29 +341,21 @@ def encode_taf_batch(dat, seq_offsets, shape, state, t_start, window_us=10000, n
     """
     H, W = int(shape[0]), int(shape[1])
     K = int(volume_bins)
-    offs = [int(o) for o in seq_offsets]
-    B = len(offs) - 1
-    if B < 1 or B > _lib.MAX_SEQUENCES:
-        raise ValueError(f"1..{_lib.MAX_SEQUENCES} sequences per call")
+    offs, B = _sequences(seq_offsets, _records(dat))
     if not FAST_PATH_ENABLED:
-        raise NotImplementedError("the fast path is switched off for this job (dist.agree_fast_path: a rank failed the self-test)")
-    t0 = [int(t_start)] * B if not hasattr(t_start, "__len__") else [int(t) for t in t_start]
+        raise NotImplementedError(_FAST_PATH_OFF)
+    t0 = _per_item(t_start, B, "t_start")
     assert state.dtype == torch.float32 and state.is_contiguous() and tuple(state.shape) == (B, H, W, 2, K)
     d, desc = _events_dat(dat, xmap, ymap)
     ws = _batch_workspace(offs[-1] - offs[0], B, H, W, window_us, d.device)
     if ws is None:
         raise NotImplementedError("shape outside the fast TAF path")
-    u8 = torch.empty((B, K, 2, H, W), dtype=torch.uint8, device=d.device) if want_u8 else None
-    view = torch.empty((B, 2 * K, H, W), dtype=torch.float32, device=d.device) if want_view else None
+    view, u8 = _outputs((B, 2 * K, H, W), d.device, want_view, want_u8, u8_shape=(B, K, 2, H, W))
     flags = _lib.TAF_U8_FLIP_K if flip_k else 0
     rc = _lib.load().frlw_taf_encode_batch(C.byref(desc), (C.c_int64 * (B + 1))(*offs), (C.c_int64 * B)(*t0), B, H, W, K,
                                            int(window_us), int(n_windows), _ptr(state), _ptr(view), _ptr(u8), flags,
                                            _ptr(ws), ws.numel(), _stream())
-    if rc == _lib.FRLW_ERR_UNSUPPORTED:
-        raise NotImplementedError("window / shape outside the fast TAF path")
-    _lib.check(rc, "encode_taf_batch")
-    if check:
-        _finish(ws, "encode_taf_batch")
+    _run(rc, "encode_taf_batch", ws, check, "window / shape outside the fast TAF path")
     return u8, view
 
 
@@ -335,11 +388,8 @@ def encode_taf_stripe(dat, seq_offsets, shape, stripe, state, t_start, window_us
     if not (0 <= y_lo < y_hi <= H):
         raise ValueError("stripe must be (y_lo, y_hi) with 0 <= y_lo < y_hi <= H")
     K = int(volume_bins)
-    offs = [int(o) for o in seq_offsets]
-    B = len(offs) - 1
-    if B < 1 or B > _lib.MAX_SEQUENCES:
-        raise ValueError(f"1..{_lib.MAX_SEQUENCES} sequences per call")
-    t0 = [int(t_start)] * B if not hasattr(t_start, "__len__") else [int(t) for t in t_start]
+    offs, B = _sequences(seq_offsets, _records(dat))
+    t0 = _per_item(t_start, B, "t_start")
     assert state.dtype == torch.float32 and state.is_contiguous() and tuple(state.shape) == (B, rows, W, 2, K)
     d, desc = _events_dat(dat, xmap, ymap)
     ws = _batch_workspace(offs[-1] - offs[0], B, rows, W, window_us, d.device, slot=("stripe", y_lo, y_hi))
@@ -349,24 +399,44 @@ def encode_taf_stripe(dat, seq_offsets, shape, stripe, state, t_start, window_us
     c_offs, c_t0 = (C.c_int64 * (B + 1))(*offs), (C.c_int64 * B)(*t0)
     rc = lib.frlw_taf_stripe_partition(C.byref(desc), c_offs, c_t0, B, H, W, y_lo, rows, K, int(window_us), int(n_windows),
                                        _ptr(ws), ws.numel(), _stream())
-    if rc == _lib.FRLW_ERR_UNSUPPORTED:
-        raise NotImplementedError("window / shape outside the fast TAF path")
-    _lib.check(rc, "encode_taf_stripe (partition)")
+    _run(rc, "encode_taf_stripe (partition)", ws, False, "window / shape outside the fast TAF path")
     off = int(lib.frlw_taf_stripe_window_masks(_ptr(ws))) - ws.data_ptr()
     masks = ws[off:off + 8 * B].view(torch.int64)  # the kernels' own words: reduced in place, read by the second half
     if exchange is not None:
         exchange(masks)
     elif dist.is_available() and dist.is_initialized():  # (also a one-rank group: the collective is the same code path)
         _or_reduce_window_masks(masks, group)
-    u8 = torch.empty((B, K, 2, rows, W), dtype=torch.uint8, device=d.device) if want_u8 else None
-    view = torch.empty((B, 2 * K, rows, W), dtype=torch.float32, device=d.device) if want_view else None
+    view, u8 = _outputs((B, 2 * K, rows, W), d.device, want_view, want_u8, u8_shape=(B, K, 2, rows, W))
     flags = _lib.TAF_U8_FLIP_K if flip_k else 0
-    _lib.check(lib.frlw_taf_stripe_finish(C.byref(desc), c_offs, c_t0, B, H, W, y_lo, rows, K, int(window_us), int(n_windows),
-                                          _ptr(state), _ptr(view), _ptr(u8), flags, _ptr(ws), ws.numel(), _stream()),
-               "encode_taf_stripe (finish)")
-    if check:
-        _finish(ws, "encode_taf_stripe")
+    rc = lib.frlw_taf_stripe_finish(C.byref(desc), c_offs, c_t0, B, H, W, y_lo, rows, K, int(window_us), int(n_windows),
+                                    _ptr(state), _ptr(view), _ptr(u8), flags, _ptr(ws), ws.numel(), _stream())
+    _run(rc, "encode_taf_stripe (finish)", ws, check)
     return u8, view
+
+
+def _fast_or_general(n, device, check, fast, batch_call):
+    """The ``fast`` argument of ``encode_taf_dat`` / ``encode_ev_dat`` for ``n`` records: ``batch_call()`` makes the batched call
+    with one sequence and returns its pair.  Returns that pair without its batch axis, or ``_GENERAL``: the fast path was not
+    asked for, is switched off, refused the shape / window or found an event outside its contract (it wrote nothing then)."""
+    if fast == "auto":
+        fast = bool(check) and n >= FAST_MIN_EVENTS
+    if not (fast and FAST_PATH_ENABLED):
+        return _GENERAL
+    if check:
+        # The fall-back below takes a ValueError / IndexError of the fast call to mean "THIS call wrote nothing".  The status
+        # word it reads is sticky: an earlier unchecked call on the same workspace may have left its error there.  Drain
+        # that first and let it propagate -- it belongs to the earlier call, and swallowing it here would run the general
+        # path on a state the fast call has already stepped.
+        pending = _WORKSPACES.get(("batch", device.index, _stream_id()))
+        if pending is not None:
+            _finish(pending, "an earlier unchecked encoder call on this stream")
+    try:
+        a, b = batch_call()
+    except NotImplementedError:  # the shape / window or the device is outside the fast path
+        return _GENERAL
+    except (ValueError, IndexError):  # out-of-span / out-of-frame events: nothing was written, the general path places or reports them
+        return _GENERAL
+    return (None if a is None else a[0]), (None if b is None else b[0])
 
 
 def encode_taf_dat(dat, shape, state, t_start, window_us=10000, n_windows=8, volume_bins=8, want_view=False,
@@ -387,38 +457,30 @@ def encode_taf_dat(dat, shape, state, t_start, window_us=10000, n_windows=8, vol
     H, W = int(shape[0]), int(shape[1])
     K = int(volume_bins)
     assert state.dtype == torch.float32 and state.is_contiguous() and tuple(state.shape) == (H, W, 2, K)
-    n = dat.numel() * dat.element_size() // 8
-    if fast == "auto":
-        fast = bool(check) and n >= FAST_MIN_EVENTS
-    fast = fast and FAST_PATH_ENABLED
-    if fast:
-        if check:
-            # The fall-back below takes a ValueError / IndexError of the fast call to mean "THIS call wrote nothing".  The status
-            # word it reads is sticky: an earlier unchecked call on the same workspace may have left its error there.  Drain
-            # that first and let it propagate -- it belongs to the earlier call, and swallowing it here would run the general
-            # path on a state the fast call has already stepped.
-            pending = _WORKSPACES.get(("batch", dat.device.index, torch.cuda.current_stream().cuda_stream))
-            if pending is not None:
-                _raise_deferred_of(pending, "an earlier unchecked encoder call on this stream")
-        try:
-            u8, view = encode_taf_batch(dat, [0, n], (H, W), state.view(1, H, W, 2, K), t_start, window_us, n_windows, K,
-                                        want_view, want_u8, flip_k, xmap, ymap, check)
-            return (None if u8 is None else u8[0]), (None if view is None else view[0])
-        except NotImplementedError:
-            pass
-        except (ValueError, IndexError):
-            pass  # out-of-span / out-of-frame events: nothing was written, the general path places or reports them
+    n = _records(dat)
+    served = _fast_or_general(n, dat.device, check, fast, lambda: encode_taf_batch(
+        dat, [0, n], (H, W), state.view(1, H, W, 2, K), t_start, window_us, n_windows, K, want_view, want_u8, flip_k, xmap, ymap, check))
+    if served is not _GENERAL:
+        return served
     d, desc = _events_dat(dat, xmap, ymap)
-    u8 = torch.empty((K, 2, H, W), dtype=torch.uint8, device=d.device) if want_u8 else None
-    view = torch.empty((2 * K, H, W), dtype=torch.float32, device=d.device) if want_view else None
+    view, u8 = _outputs((2 * K, H, W), d.device, want_view, want_u8, u8_shape=(K, 2, H, W))
     ws = _workspace(desc.n, H, W, d.device)
     flags = _lib.TAF_U8_FLIP_K if flip_k else 0
-    _lib.check(_lib.load().frlw_taf_encode(C.byref(desc), H, W, K, int(t_start), int(window_us), int(n_windows),
-                                           _ptr(state), _ptr(view), _ptr(u8), flags, _ptr(ws), ws.numel(), _stream()),
-               "encode_taf_dat")
-    if check:
-        _finish(ws, "encode_taf_dat")
+    _run(_lib.load().frlw_taf_encode(C.byref(desc), H, W, K, int(t_start), int(window_us), int(n_windows), _ptr(state), _ptr(view),
+                                     _ptr(u8), flags, _ptr(ws), ws.numel(), _stream()), "encode_taf_dat", ws, check)
     return u8, view
+
+
+def _group_cuts(rows, start_time, window_us, n_groups):
+    """Where the time-sorted records ``rows`` ``(n, 8)`` uint8 are cut into ``n_groups`` groups of ``_MAX_WINDOWS`` windows from
+    ``start_time`` on: ``n_groups + 1`` record indices, 0 first and ``n`` last.  An event on a group boundary belongs to the later
+    group (``right=False``), as in the reference's ``z`` column (generate_taf.py:197-203).  One host synchronisation if it cuts."""
+    n = rows.shape[0]
+    if n_groups < 2 or not n:
+        return [0] * n_groups + [n]
+    t = rows.view(torch.int32).reshape(-1, 2)[:, 0].to(torch.int64) & 0xFFFFFFFF
+    bounds = torch.tensor([start_time + g * _MAX_WINDOWS * window_us for g in range(1, n_groups)], dtype=torch.int64, device=t.device)
+    return [0] + [int(c) for c in torch.searchsorted(t, bounds, right=False).tolist()] + [n]
 
 
 def encode_taf_label(dat, shape, state, start_time, window_us, bins, volume_bins=8, flip_k=True, xmap=None, ymap=None,
@@ -441,31 +503,21 @@ def encode_taf_label(dat, shape, state, start_time, window_us, bins, volume_bins
     """
     H, W = int(shape[0]), int(shape[1])
     K = int(volume_bins)
-    lib = _lib.load()
-    max_w = 64
-    n = dat.numel() * dat.element_size() // 8
     if bins <= 0:
         vol = state.permute(3, 2, 0, 1).contiguous()  # (K, 2, H, W), the view of :55
         for _ in range(2 + int(stale_transforms)):    # :226-227 on the stale, already transformed volume
             vol = leaky_transform(vol)
         u8 = quantize_u8(vol)
         return torch.flip(u8, dims=[0]).contiguous() if flip_k else u8
-    cuts = [0]
-    if bins > max_w and n:
-        t = dat.contiguous().view(torch.int32).reshape(-1, 2)[:, 0].to(torch.int64) & 0xFFFFFFFF
-        bounds = torch.tensor([start_time + g * max_w * window_us for g in range(1, (bins + max_w - 1) // max_w)],
-                              dtype=torch.int64, device=t.device)
-        cuts += [int(c) for c in torch.searchsorted(t, bounds, right=False).tolist()]
-    elif bins > max_w:
-        cuts += [0] * ((bins + max_w - 1) // max_w - 1)
-    cuts.append(n)
     rows = dat.contiguous().view(torch.uint8).reshape(-1, 8)
+    n_groups = (bins + _MAX_WINDOWS - 1) // _MAX_WINDOWS
+    cuts = _group_cuts(rows, start_time, window_us, n_groups)
     u8 = None
-    for g in range(len(cuts) - 1):
-        nw = min(max_w, bins - g * max_w)
-        last = g == len(cuts) - 2
-        u8, _ = encode_taf_dat(rows[cuts[g]:cuts[g + 1]], (H, W), state, start_time + g * max_w * window_us, window_us, nw, K,
-                               want_view=False, want_u8=last, flip_k=flip_k, xmap=xmap, ymap=ymap, check=check, fast=fast)
+    for g in range(n_groups):
+        nw = min(_MAX_WINDOWS, bins - g * _MAX_WINDOWS)
+        u8, _ = encode_taf_dat(rows[cuts[g]:cuts[g + 1]], (H, W), state, start_time + g * _MAX_WINDOWS * window_us, window_us, nw, K,
+                               want_view=False, want_u8=(g == n_groups - 1), flip_k=flip_k, xmap=xmap, ymap=ymap, check=check,
+                               fast=fast)
     return u8
 
 
@@ -490,24 +542,15 @@ def encode_taf_chain(dat, shape, state, start_time, window_us, bins, volume_bins
     if not bins or any(b <= 0 for b in bins):
         raise ValueError("bins: a non-empty list of positive window counts")
     assert state.dtype == torch.float32 and state.is_contiguous() and tuple(state.shape) == (H, W, 2, K)
-    max_w = 64
     total = sum(bins)
-    n_groups = (total + max_w - 1) // max_w
+    n_groups = (total + _MAX_WINDOWS - 1) // _MAX_WINDOWS
     masks = [0] * n_groups   # per group: bit w = a snapshot after the group's window w
     end = 0
     for b in bins:
         end += b
-        masks[(end - 1) // max_w] |= 1 << ((end - 1) % max_w)
+        masks[(end - 1) // _MAX_WINDOWS] |= 1 << ((end - 1) % _MAX_WINDOWS)
     rows = dat.contiguous().view(torch.uint8).reshape(-1, 8)
-    n = rows.shape[0]
-    cuts = [0]
-    if n_groups > 1 and n:
-        t = rows.view(torch.int32).reshape(-1, 2)[:, 0].to(torch.int64) & 0xFFFFFFFF
-        bounds = torch.tensor([start_time + g * max_w * window_us for g in range(1, n_groups)], dtype=torch.int64, device=t.device)
-        cuts += [int(c) for c in torch.searchsorted(t, bounds, right=False).tolist()]
-    else:
-        cuts += [0] * (n_groups - 1)
-    cuts.append(n)
+    cuts = _group_cuts(rows, start_time, window_us, n_groups)
     snaps = torch.empty((len(bins), K, 2, H, W), dtype=torch.uint8, device=rows.device)
     ws = _workspace(max(cuts[g + 1] - cuts[g] for g in range(n_groups)), H, W, rows.device)
     flags = _lib.TAF_U8_FLIP_K if flip_k else 0
@@ -515,18 +558,16 @@ def encode_taf_chain(dat, shape, state, start_time, window_us, bins, volume_bins
     done = 0
     for g in range(n_groups):
         d, desc = _events_dat(rows[cuts[g]:cuts[g + 1]], xmap, ymap)
-        nw = min(max_w, total - g * max_w)
-        t0 = int(start_time) + g * max_w * int(window_us)
+        nw = min(_MAX_WINDOWS, total - g * _MAX_WINDOWS)
+        t0 = int(start_time) + g * _MAX_WINDOWS * int(window_us)
         if masks[g]:
-            _lib.check(lib.frlw_taf_encode_chain(C.byref(desc), H, W, K, t0, int(window_us), nw, masks[g], _ptr(state),
-                                                 C.c_void_p(snaps[done].data_ptr()), flags, _ptr(ws), ws.numel(), _stream()),
-                       "encode_taf_chain")
+            rc = lib.frlw_taf_encode_chain(C.byref(desc), H, W, K, t0, int(window_us), nw, masks[g], _ptr(state),
+                                           C.c_void_p(snaps[done].data_ptr()), flags, _ptr(ws), ws.numel(), _stream())
             done += bin(masks[g]).count("1")
         else:   # inside a step longer than 64 windows: the state moves, nothing is handed out
-            _lib.check(lib.frlw_taf_encode(C.byref(desc), H, W, K, t0, int(window_us), nw, _ptr(state), None, None, flags,
-                                           _ptr(ws), ws.numel(), _stream()), "encode_taf_chain")
-    if check:
-        _finish(ws, "encode_taf_chain")
+            rc = lib.frlw_taf_encode(C.byref(desc), H, W, K, t0, int(window_us), nw, _ptr(state), None, None, flags,
+                                     _ptr(ws), ws.numel(), _stream())
+        _run(rc, "encode_taf_chain", ws, check and g == n_groups - 1)
     return snaps
 
 
@@ -540,30 +581,16 @@ def encode_ev_dat(dat, shape, t_end, window_us, volume_bins=5, want_f32=True, wa
     otherwise, or the window does not fit its 4-byte records, the general path runs -- same bits either way.  ``fast=True`` with
     ``check=False`` is an explicit opt-in whose caller owes a ``raise_deferred()`` (a violation leaves the outputs unwritten)."""
     H, W = int(shape[0]), int(shape[1])
-    n = dat.numel() * dat.element_size() // 8
-    if fast == "auto":
-        fast = bool(check) and n >= FAST_MIN_EVENTS
-    fast = fast and FAST_PATH_ENABLED
-    if fast:
-        if check:  # (an earlier unchecked call's error must not be mistaken for this call's: encode_taf_dat explains)
-            pending = _WORKSPACES.get(("batch", dat.device.index, torch.cuda.current_stream().cuda_stream))
-            if pending is not None:
-                _raise_deferred_of(pending, "an earlier unchecked encoder call on this stream")
-        try:
-            out, u8 = encode_ev_batch(dat, [0, n], (H, W), t_end, window_us, volume_bins, want_f32, want_u8, xmap, ymap, check)
-            return (None if out is None else out[0]), (None if u8 is None else u8[0])
-        except NotImplementedError:
-            pass
-        except (ValueError, IndexError):
-            pass  # an event behind t_end / outside the frame: nothing was written, the general path places or reports it
+    n = _records(dat)
+    served = _fast_or_general(n, dat.device, check, fast, lambda: encode_ev_batch(
+        dat, [0, n], (H, W), t_end, window_us, volume_bins, want_f32, want_u8, xmap, ymap, check))
+    if served is not _GENERAL:
+        return served
     d, desc = _events_dat(dat, xmap, ymap)
-    out = torch.empty((2 * volume_bins, H, W), dtype=torch.float32, device=d.device) if want_f32 else None
-    u8 = torch.empty((2 * volume_bins, H, W), dtype=torch.uint8, device=d.device) if want_u8 else None
+    out, u8 = _outputs((2 * volume_bins, H, W), d.device, want_f32, want_u8)
     ws = _workspace(desc.n, H, W, d.device)
-    _lib.check(_lib.load().frlw_ev_encode(C.byref(desc), H, W, int(volume_bins), int(t_end), int(window_us), _ptr(out),
-                                          _ptr(u8), _ptr(ws), ws.numel(), _stream()), "encode_ev_dat")
-    if check:
-        _finish(ws, "encode_ev_dat")
+    _run(_lib.load().frlw_ev_encode(C.byref(desc), H, W, int(volume_bins), int(t_end), int(window_us), _ptr(out), _ptr(u8),
+                                    _ptr(ws), ws.numel(), _stream()), "encode_ev_dat", ws, check)
     return out, u8
 
 
@@ -576,26 +603,18 @@ def encode_ev_batch(dat, seq_offsets, shape, t_end, window_us, volume_bins=5, wa
     sequence.  An event behind its ``t_end`` is outside the contract: with ``check`` it raises ``ValueError`` (nothing is
     written); unchecked callers owe a ``raise_deferred()``.  ``NotImplementedError``: shape / window outside the path."""
     H, W = int(shape[0]), int(shape[1])
-    offs = [int(o) for o in seq_offsets]
-    B = len(offs) - 1
-    if B < 1 or B > _lib.MAX_SEQUENCES:
-        raise ValueError(f"1..{_lib.MAX_SEQUENCES} sequences per call")
+    offs, B = _sequences(seq_offsets, _records(dat))
     if not FAST_PATH_ENABLED:
-        raise NotImplementedError("the fast path is switched off for this job (dist.agree_fast_path: a rank failed the self-test)")
-    te = [int(t_end)] * B if not hasattr(t_end, "__len__") else [int(t) for t in t_end]
+        raise NotImplementedError(_FAST_PATH_OFF)
+    te = _per_item(t_end, B, "t_end")
     d, desc = _events_dat(dat, xmap, ymap)
     ws = _batch_workspace(offs[-1] - offs[0], B, H, W, window_us, d.device)
     if ws is None:
         raise NotImplementedError("shape outside the batched Event Volume path")
-    out = torch.empty((B, 2 * volume_bins, H, W), dtype=torch.float32, device=d.device) if want_f32 else None
-    u8 = torch.empty((B, 2 * volume_bins, H, W), dtype=torch.uint8, device=d.device) if want_u8 else None
+    out, u8 = _outputs((B, 2 * volume_bins, H, W), d.device, want_f32, want_u8)
     rc = _lib.load().frlw_ev_encode_batch(C.byref(desc), (C.c_int64 * (B + 1))(*offs), (C.c_int64 * B)(*te), B, H, W,
                                           int(volume_bins), int(window_us), _ptr(out), _ptr(u8), _ptr(ws), ws.numel(), _stream())
-    if rc == _lib.FRLW_ERR_UNSUPPORTED:
-        raise NotImplementedError("window / shape outside the batched Event Volume path")
-    _lib.check(rc, "encode_ev_batch")
-    if check:
-        _finish(ws, "encode_ev_batch")
+    _run(rc, "encode_ev_batch", ws, check, "window / shape outside the batched Event Volume path")
     return out, u8
 
 
@@ -621,36 +640,23 @@ def encode_ev_ranges(dat, ranges, shape, t_end, window_us, volume_bins=5, want_f
     ``check``, for an event behind its ``t_end``: nothing is written; ``NotImplementedError``: shape / window outside the path, the
     fast path switched off).  A workspace slot of its own."""
     H, W = int(shape[0]), int(shape[1])
-    rng = [(int(lo), int(hi)) for lo, hi in ranges]
+    rng = _ranges(ranges, _records(dat), "windows")
     B = len(rng)
-    if B < 1 or B > _lib.MAX_SEQUENCES:
-        raise ValueError(f"1..{_lib.MAX_SEQUENCES} windows per call")
     if not want_f32 and not want_u8:
         raise ValueError("nothing to return: want_f32 or want_u8")
-    te = [int(t_end)] * B if not hasattr(t_end, "__len__") else [int(t) for t in t_end]
-    if len(te) != B:
-        raise ValueError("one `t_end` per window")
-    n = dat.numel() * dat.element_size() // 8
-    for lo, hi in rng:
-        if lo < 0 or hi < lo or hi > n:
-            raise ValueError(f"record range ({lo}, {hi}) outside 0 <= lo <= hi <= {n}")
+    te = _per_item(t_end, B, "t_end")
     if not FAST_PATH_ENABLED:
-        raise NotImplementedError("the fast path is switched off for this job (dist.agree_fast_path: a rank failed the self-test)")
+        raise NotImplementedError(_FAST_PATH_OFF)
     d, desc = _events_dat(dat, xmap, ymap)
     need = _lib.load().frlw_ev_ranges_workspace_bytes(sum(hi - lo for lo, hi in rng), B, H, W, int(window_us))
     if need == 0:
         raise NotImplementedError("shape / window outside the ranged Event Volume path")
     ws = _slot_workspace(need, d.device, "ev_ranges")
-    out = torch.empty((B, 2 * volume_bins, H, W), dtype=torch.float32, device=d.device) if want_f32 else None
-    u8 = torch.empty((B, 2 * volume_bins, H, W), dtype=torch.uint8, device=d.device) if want_u8 else None
+    out, u8 = _outputs((B, 2 * volume_bins, H, W), d.device, want_f32, want_u8)
     rc = _lib.load().frlw_ev_encode_ranges(C.byref(desc), (C.c_int64 * B)(*[r[0] for r in rng]), (C.c_int64 * B)(*[r[1] for r in rng]),
                                            (C.c_int64 * B)(*te), B, H, W, int(volume_bins), int(window_us), _ptr(out), _ptr(u8),
                                            _ptr(ws), ws.numel(), _stream())
-    if rc == _lib.FRLW_ERR_UNSUPPORTED:
-        raise NotImplementedError("window / shape outside the ranged Event Volume path")
-    _lib.check(rc, "encode_ev_ranges")
-    if check:
-        _finish(ws, "encode_ev_ranges")
+    _run(rc, "encode_ev_ranges", ws, check, "window / shape outside the ranged Event Volume path")
     return out, u8
 
 
@@ -658,13 +664,10 @@ def encode_eci_dat(dat, shape, want_f32=True, want_u8=False, xmap=None, ymap=Non
     """generate_eventcountimage.py:155-180 on device (the caller has cut the last ``events_window`` records)."""
     H, W = int(shape[0]), int(shape[1])
     d, desc = _events_dat(dat, xmap, ymap)
-    out = torch.empty((2, H, W), dtype=torch.float32, device=d.device) if want_f32 else None
-    u8 = torch.empty((2, H, W), dtype=torch.uint8, device=d.device) if want_u8 else None
+    out, u8 = _outputs((2, H, W), d.device, want_f32, want_u8)
     ws = _workspace(desc.n, H, W, d.device)
-    _lib.check(_lib.load().frlw_eci_encode(C.byref(desc), H, W, _ptr(out), _ptr(u8), _ptr(ws), ws.numel(), _stream()),
-               "encode_eci_dat")
-    if check:
-        _finish(ws, "encode_eci_dat")
+    _run(_lib.load().frlw_eci_encode(C.byref(desc), H, W, _ptr(out), _ptr(u8), _ptr(ws), ws.numel(), _stream()),
+         "encode_eci_dat", ws, check)
     return out, u8
 
 
@@ -673,33 +676,19 @@ def encode_sae_dat(dat, shape, lamdas, memory, now, window_us, want_f32=True, wa
     """generate_surfaceofactiveevents.py:183-194 on device -> (f32 or None, u8 or None, new memory)."""
     H, W = int(shape[0]), int(shape[1])
     d, desc = _events_dat(dat, xmap, ymap)
-    lam = (C.c_double * len(lamdas))(*[float(l) for l in lamdas])
-    out = torch.empty((2 * len(lamdas), H, W), dtype=torch.float32, device=d.device) if want_f32 else None
-    u8 = torch.empty((2 * len(lamdas), H, W), dtype=torch.uint8, device=d.device) if want_u8 else None
+    lam, L = _lamdas(lamdas)
+    out, u8 = _outputs((2 * L, H, W), d.device, want_f32, want_u8)
     mem_out = torch.empty((2, H, W), dtype=torch.float32, device=d.device)
     mem_in = None if memory is None else memory.to(torch.float32).contiguous()
     ws = _workspace(desc.n, H, W, d.device)
-    _lib.check(_lib.load().frlw_sae_encode(C.byref(desc), H, W, lam, len(lamdas), _ptr(mem_in), _ptr(mem_out), int(now),
-                                           int(window_us), _ptr(out), _ptr(u8), _ptr(ws), ws.numel(), _stream()),
-               "encode_sae_dat")
-    if check:
-        _finish(ws, "encode_sae_dat")
+    _run(_lib.load().frlw_sae_encode(C.byref(desc), H, W, lam, L, _ptr(mem_in), _ptr(mem_out), int(now), int(window_us), _ptr(out),
+                                     _ptr(u8), _ptr(ws), ws.numel(), _stream()), "encode_sae_dat", ws, check)
     return out, u8, mem_out
 
 
 # ------------------------------------------------------------------------------------------------
 # batched Event Count Image / Surface of Active Events (csrc/encoders_batch.hip)
 # ------------------------------------------------------------------------------------------------
-def _slot_workspace(need, device, slot):
-    """The workspace of ``slot`` on the current stream, grown to ``need`` bytes."""
-    key = (slot, device.index, torch.cuda.current_stream().cuda_stream)
-    ws = _WORKSPACES.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _new_workspace(ws, need, device)
-        _WORKSPACES[key] = ws
-    return ws
-
-
 def encode_eci_batch(dat, ranges, shape, want_f32=True, want_u8=False, xmap=None, ymap=None, check=True):
     """generate_eventcountimage.py:155-180 for a batch of record windows in one launch sequence (``frlw_eci_encode_batch``):
     window ``b`` is the records ``dat[lo:hi]`` of ``ranges[b] = (lo, hi)``; windows may overlap, nest or be empty.  Returns
@@ -708,30 +697,20 @@ def encode_eci_batch(dat, ranges, shape, want_f32=True, want_u8=False, xmap=None
     ``IndexError``, unchecked callers owe a ``raise_deferred()``.  ``NotImplementedError``: shape outside the path.  The counts
     are integer atomics, so this path does not depend on the LDS lane-order self-test (``FAST_PATH_ENABLED`` is not consulted)."""
     H, W = int(shape[0]), int(shape[1])
-    rng = [(int(lo), int(hi)) for lo, hi in ranges]
+    n = _records(dat)
+    rng = _ranges(ranges, n, "windows")
     B = len(rng)
-    if B < 1 or B > _lib.MAX_SEQUENCES:
-        raise ValueError(f"1..{_lib.MAX_SEQUENCES} windows per call")
     if not want_f32 and not want_u8:
         raise ValueError("nothing to return: want_f32 or want_u8")
-    n = dat.numel() * dat.element_size() // 8
-    for lo, hi in rng:
-        if lo < 0 or hi < lo or hi > n:
-            raise ValueError(f"record range ({lo}, {hi}) outside 0 <= lo <= hi <= {n}")
     d, desc = _events_dat(dat, xmap, ymap)
     need = _lib.load().frlw_eci_batch_workspace_bytes(n, B, H, W)
     if need == 0:
         raise NotImplementedError("shape outside the batched Event Count Image path")
     ws = _slot_workspace(need, d.device, "eci_batch")
-    out = torch.empty((B, 2, H, W), dtype=torch.float32, device=d.device) if want_f32 else None
-    u8 = torch.empty((B, 2, H, W), dtype=torch.uint8, device=d.device) if want_u8 else None
+    out, u8 = _outputs((B, 2, H, W), d.device, want_f32, want_u8)
     rc = _lib.load().frlw_eci_encode_batch(C.byref(desc), (C.c_int64 * B)(*[r[0] for r in rng]), (C.c_int64 * B)(*[r[1] for r in rng]),
                                            B, H, W, _ptr(out), _ptr(u8), _ptr(ws), ws.numel(), _stream())
-    if rc == _lib.FRLW_ERR_UNSUPPORTED:
-        raise NotImplementedError("input outside the batched Event Count Image path")
-    _lib.check(rc, "encode_eci_batch")
-    if check:
-        _finish(ws, "encode_eci_batch")
+    _run(rc, "encode_eci_batch", ws, check, "input outside the batched Event Count Image path")
     return out, u8
 
 
@@ -745,18 +724,10 @@ def encode_sae_batch(dat, seq_offsets, shape, lamdas, memory, now, window_us, wa
     ``encode_eci_batch`` (only the coordinate maps can report an event: one outside the frame is dropped).  Integer atomics: no
     dependence on the LDS lane-order self-test."""
     H, W = int(shape[0]), int(shape[1])
-    offs = [int(o) for o in seq_offsets]
-    B = len(offs) - 1
-    if B < 1 or B > _lib.MAX_SEQUENCES:
-        raise ValueError(f"1..{_lib.MAX_SEQUENCES} sequences per call")
-    nows = [int(now)] * B if not hasattr(now, "__len__") else [int(t) for t in now]
-    if len(nows) != B:
-        raise ValueError("one `now` per sequence")
-    if len(lamdas) > _lib.MAX_LAMDAS:
-        raise ValueError(f"at most {_lib.MAX_LAMDAS} lamdas")
-    n = dat.numel() * dat.element_size() // 8
-    if offs[0] < 0 or offs[-1] > n or any(b < a for a, b in zip(offs, offs[1:])):
-        raise ValueError(f"seq_offsets must ascend inside 0..{n}")
+    n = _records(dat)
+    offs, B = _sequences(seq_offsets, n)
+    nows = _per_item(now, B, "now")
+    lam, L = _lamdas(lamdas)
     if memory is not None and tuple(memory.shape) != (B, 2, H, W):
         raise ValueError(f"memory must be ({B}, 2, {H}, {W})")
     d, desc = _events_dat(dat, xmap, ymap)
@@ -764,20 +735,13 @@ def encode_sae_batch(dat, seq_offsets, shape, lamdas, memory, now, window_us, wa
     if need == 0:
         raise NotImplementedError("shape outside the batched Surface of Active Events path")
     ws = _slot_workspace(need, d.device, "sae_batch")
-    L = len(lamdas)
-    lam = (C.c_double * max(L, 1))(*[float(l) for l in lamdas])
-    out = torch.empty((B, 2 * L, H, W), dtype=torch.float32, device=d.device) if want_f32 else None
-    u8 = torch.empty((B, 2 * L, H, W), dtype=torch.uint8, device=d.device) if want_u8 else None
+    out, u8 = _outputs((B, 2 * L, H, W), d.device, want_f32, want_u8)
     mem_out = torch.empty((B, 2, H, W), dtype=torch.float32, device=d.device)
     mem_in = None if memory is None else memory.to(torch.float32).contiguous()
     rc = _lib.load().frlw_sae_encode_batch(C.byref(desc), (C.c_int64 * (B + 1))(*offs), (C.c_int64 * B)(*nows), B, H, W, lam, L,
                                            _ptr(mem_in), _ptr(mem_out), int(window_us), _ptr(out), _ptr(u8), _ptr(ws), ws.numel(),
                                            _stream())
-    if rc == _lib.FRLW_ERR_UNSUPPORTED:
-        raise NotImplementedError("input outside the batched Surface of Active Events path")
-    _lib.check(rc, "encode_sae_batch")
-    if check:
-        _finish(ws, "encode_sae_batch")
+    _run(rc, "encode_sae_batch", ws, check, "input outside the batched Surface of Active Events path")
     return out, u8, mem_out
 
 
@@ -793,16 +757,11 @@ def encode_sae_chain(dat, steps, shape, lamdas, memory, want_f32=True, want_u8=F
     H, W = int(shape[0]), int(shape[1])
     steps = [tuple(s) for s in steps]
     S = len(steps)
-    if S < 1 or S > _lib.MAX_SEQUENCES:
-        raise ValueError(f"1..{_lib.MAX_SEQUENCES} steps per call")
     if any(len(s) != 5 for s in steps):
         raise ValueError("a step is (lo, hi, now, window_us, emit)")
-    if len(lamdas) > _lib.MAX_LAMDAS:
-        raise ValueError(f"at most {_lib.MAX_LAMDAS} lamdas")
-    n = dat.numel() * dat.element_size() // 8
-    for lo, hi, _, _, _ in steps:
-        if int(lo) < 0 or int(hi) < int(lo) or int(hi) > n:
-            raise ValueError(f"record range ({lo}, {hi}) outside 0 <= lo <= hi <= {n}")
+    n = _records(dat)
+    _ranges([s[:2] for s in steps], n, "steps")
+    lam, L = _lamdas(lamdas)
     if memory is not None and tuple(memory.shape) != (2, H, W):
         raise ValueError(f"memory must be (2, {H}, {W})")
     E = sum(1 for s in steps if s[4])
@@ -813,19 +772,12 @@ def encode_sae_chain(dat, steps, shape, lamdas, memory, want_f32=True, want_u8=F
     if need == 0:
         raise NotImplementedError("shape outside the chained Surface of Active Events path")
     ws = _slot_workspace(need, d.device, "sae_chain")
-    L = len(lamdas)
-    lam = (C.c_double * max(L, 1))(*[float(l) for l in lamdas])
-    out = torch.empty((E, 2 * L, H, W), dtype=torch.float32, device=d.device) if (want_f32 and E) else None
-    u8 = torch.empty((E, 2 * L, H, W), dtype=torch.uint8, device=d.device) if (want_u8 and E) else None
+    out, u8 = _outputs((E, 2 * L, H, W), d.device, want_f32 and E, want_u8 and E)
     mem_out = torch.empty((2, H, W), dtype=torch.float32, device=d.device)
     mem_in = None if memory is None else memory.to(torch.float32).contiguous()
     col = lambda k: (C.c_int64 * S)(*[int(s[k]) for s in steps])  # noqa: E731
     rc = _lib.load().frlw_sae_encode_chain(C.byref(desc), col(0), col(1), col(2), col(3), (C.c_uint8 * S)(*[1 if s[4] else 0 for s in steps]),
                                            S, H, W, lam, L, _ptr(mem_in), _ptr(mem_out), _ptr(out), _ptr(u8), _ptr(ws), ws.numel(),
                                            _stream())
-    if rc == _lib.FRLW_ERR_UNSUPPORTED:
-        raise NotImplementedError("input outside the chained Surface of Active Events path")
-    _lib.check(rc, "encode_sae_chain")
-    if check:
-        _finish(ws, "encode_sae_chain")
+    _run(rc, "encode_sae_chain", ws, check, "input outside the chained Surface of Active Events path")
     return out, u8, mem_out

@@ -90,11 +90,8 @@ def time_surface_pairs(dat, ranges, shape, check=True):
     (``den <= 0``) is computed by ``time_surface_numpy`` from the records copied back: the device reports every window's stamp
     range, which is read once per call (one synchronisation).  ``check``: also read the status word of the call."""
     H, W = int(shape[0]), int(shape[1])
-    rng = [(int(lo), int(hi)) for lo, hi in ranges]
-    n = dat.numel() * dat.element_size() // 8
-    for lo, hi in rng:
-        if lo < 0 or hi < lo or hi > n:
-            raise ValueError(f"record range ({lo}, {hi}) outside 0 <= lo <= hi <= {n}")
+    n = er._records(dat)
+    rng = er._ranges(ranges, n)   # any number of them: cut into calls of 64 below
     d, desc = er._events_dat(dat)
     lib = _lib.load()
     out = torch.empty((len(rng), 2, H, W), dtype=torch.uint8, device=d.device)
@@ -110,12 +107,8 @@ def time_surface_pairs(dat, ranges, shape, check=True):
         pairs = out[b0:b0 + B]
         rc = lib.frlw_time_surface_batch(C.byref(desc), (C.c_int64 * B)(*[r[0] for r in part]), (C.c_int64 * B)(*[r[1] for r in part]),
                                          B, H, W, er._ptr(pairs), er._ptr(stamps), er._ptr(ws), ws.numel(), er._stream())
-        if rc == _lib.FRLW_ERR_UNSUPPORTED:
-            raise NotImplementedError("input outside the time-surface path")
-        _lib.check(rc, "time_surface_pairs")
+        er._run(rc, "time_surface_pairs", ws, check, "input outside the time-surface path")
         tally["calls"] += 1
-        if check:
-            er._finish(ws, "time_surface_pairs")
         st = stamps.cpu().numpy()
         for i in np.flatnonzero((st[:, 1] >= 0) & (st[:, 1] - CUT - st[:, 0] <= 0)):
             lo, hi = part[i]

@@ -103,3 +103,36 @@ def test_python_layer_validates_before_any_device_call():
         er.encode_sae_batch(dat, [0, 50, 100], (8, 12), lam, torch.zeros((3, 2, 8, 12)), 5, 0)
     with pytest.raises(ValueError):
         er.encode_sae_batch(dat, [0, 50, 100], (8, 12), [1e-6] * 9, None, 5, 0)
+
+
+def test_per_sequence_arguments_are_length_checked_before_any_device_call():
+    """CPU tensors again.  ctypes zero-fills a short initialiser -- ``(c_int64 * 3)(*[5])`` is ``[5, 0, 0]`` -- so a ``t_start`` /
+    ``t_end`` list one entry short would encode the last sequence from t = 0 without a word, and one entry too long raises ctypes'
+    IndexError, which in this layer means "event coordinate out of range".  Both are ValueError from the argument checks, like a
+    sequence list that descends, leaves ``dat`` or holds 0 or 65 sequences; an int applies to all and passes them (the device
+    check behind them then turns the CPU tensor down with RuntimeError)."""
+    from frlw_evd_amd import event_representation as er
+    H, W, K = 8, 12, 8
+    dat = torch.zeros((100, 8), dtype=torch.uint8)
+    two = [0, 50, 100]
+
+    def taf(offs, t_start):
+        B = len(offs) - 1
+        return er.encode_taf_batch(dat, offs, (H, W), torch.zeros((B, H, W, 2, K)), t_start, 10_000, 8, K)
+
+    def stripe(offs, t_start):
+        return er.encode_taf_stripe(dat, offs, (H, W), (0, 4), torch.zeros((len(offs) - 1, 4, W, 2, K)), t_start)
+
+    def ev(offs, t_end):
+        return er.encode_ev_batch(dat, offs, (H, W), t_end, 10_000)
+
+    for call, items in ((taf, [0]), (taf, [0, 0, 0]), (stripe, [0]), (ev, [7]), (ev, [7, 7, 7])):
+        with pytest.raises(ValueError):
+            call(two, items)
+    for call in (taf, ev):
+        for offs in ([0, 50, 20], [0, 50, 101], [0], list(range(66))):
+            with pytest.raises(ValueError):
+                call(offs, 0)
+    for call in (taf, stripe, ev):
+        with pytest.raises(RuntimeError):
+            call(two, 0)

@@ -187,6 +187,24 @@ def test_single_window_shim_takes_the_two_launch_path(er, orc):
     assert_bitexact(host(out), orc.ev_stream_dat8(late, (H, W), (H, W), 5, win, win), "late events through the fall-back")
 
 
+def test_an_earlier_unchecked_error_is_not_mistaken_for_this_calls(er, orc):
+    """The Event Volume twin of the test of this name in tests/test_taf_fast_gpu.py: the status word is sticky.  An unchecked
+    ``encode_ev_batch`` leaves an error; a later CLEAN checked ``encode_ev_dat(fast=True)`` raises that earlier error -- it does not
+    take it for its own and quietly fall back to the general path -- and once the word is drained the same call returns the
+    oracle's bits."""
+    H, W, win, bins = 53, 91, 20_000, 5
+    rec = synth.to_dat8(synth.synth_events(83, 5_000, W, H, win, t_offset=1))
+    bad = rec.copy()
+    bad["t"][-1] = win + 7  # behind t_end
+    er.raise_deferred()
+    er.encode_ev_batch(to_dev(bad), [0, len(bad)], (H, W), win, win, bins, check=False)
+    with pytest.raises(ValueError):
+        er.encode_ev_dat(to_dev(rec), (H, W), win, win, bins, fast=True)
+    er.raise_deferred()  # the word is clean (the raising call drained it): nothing to report
+    out, _ = er.encode_ev_dat(to_dev(rec), (H, W), win, win, bins, fast=True)
+    assert_bitexact(host(out), orc.ev_stream_dat8(rec, (H, W), (H, W), bins, win, win), "after the drain")
+
+
 @pytest.fixture(scope="module")
 def gather_inputs():
     """(a) one window whose hottest sub-tile list (a quarter of 300 000 events in one 8x8 block) is far above the 2048 records a
