@@ -1,7 +1,9 @@
 // taf_walk.h -- kf_taf_walk: one workgroup per sub-tile list, a window per wavefront, then the FIFO steps.
-// Expects taf_split.h (TileP), taf_fifo.h (fifo_step, fifo_mean, kMaxK) and taf_column.h; the leaky table (kLeakyTableWords, leaky.h).
+// Expects taf_split.h (TileP), taf_fifo.h (fifo_step, fifo_mean, kMaxK), taf_mean.h (mean_by_recip, kMeanTab) and taf_column.h; the leaky table
+// (kLeakyTableWords, leaky.h).
 #pragma once
 #include "taf_fifo.h"
+#include "taf_mean.h"
 #include "taf_split.h"
 
 namespace {
@@ -38,8 +40,9 @@ __device__ __forceinline__ void fifo_step_half(float (&st)[4], bool upper, bool 
 //                 `sum += t - 1` (generate_taf.py:25-26);
 //            then (sum, count) of the 256 cells go to LDS;
 //   phase 2  lane c of the first four wavefronts owns cell c: K-deep FIFO row in registers (consecutive lanes hold
-//            consecutive 32-byte rows of the (H, W, 2, K) state: whole lines), one FIFO step per window in order
-//            (generate_taf.py:27-49), skipped for windows that are empty in the whole sequence (:40-41).
+//            consecutive 32-byte rows of the (H, W, 2, K) state: whole lines), the round's means sum / (n + 1e-8) by a table
+//            reciprocal and two FMAs (taf_mean.h; by division where the wavefront holds a count of 64 or more), one FIFO step
+//            per window in order (generate_taf.py:27-49), skipped for windows that are empty in the whole sequence (:40-41).
 // (ds_add_f32 would do the ordered sum in one instruction -- it applies same-address lanes in lane order with v_add_f32
 // rounding, checked by the self-test in taf_fast.hip -- but runs at 192 cycles per wave-instruction per CU: measured, not used.)
 constexpr int kWalkWaves = 8;
@@ -61,11 +64,12 @@ template <bool K8, bool CMD = false>
 __global__ __launch_bounds__(kWalkThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void kf_taf_walk(TileP q, CmP cm, SeqTab S)
 {
     // per wavefront: kWalkSlots planes of 256 floats (plane r, cell c = the value of the cell's r-th record of the pass; +0 when
-    // there is none) + 256 ticket counters.  The (mean, count) rows phase 2 reads lie over planes 0 and 1 of their wavefront;
+    // there is none) + 256 ticket counters.  The (sum, count) rows phase 2 reads lie over planes 0 and 1 of their wavefront;
     // the CMD column and the uint8 staging at the end lie over the whole area.
     __shared__ __attribute__((aligned(16))) uint32_t s_area[kWalkWaves][kWalkWaveWords];
     __shared__ uint32_t wstart[FRLW_MAX_WINDOWS + 1];
     __shared__ uint32_t thr[kLeakyTableWords]; // thresholds + bucket table of the leaky transform (leaky_u8_bucket_n)
+    __shared__ float s_recip[kMeanTab]; // RN(1 / n) for the counts below kMeanTab ([0] = +0): the means of phase 2 (taf_mean.h)
     __shared__ int s_unsorted;
     __shared__ __attribute__((aligned(16))) uint32_t s_list[CMD ? kWalkListCap : 4]; // CMD: the gathered list, when it fits (else it goes to rec2[])
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -184,6 +188,10 @@ __global__ __launch_bounds__(kWalkThreads) __attribute__((amdgpu_waves_per_eu(8,
 #pragma unroll
         for (int i = 0; i < kWalkWaveWords / 2 / kWave; ++i) z[i * kWave + lane] = make_uint2(0u, 0u);
     }
+    // The reciprocal table, one correctly rounded division per lane of the LAST wavefront (it has no cells in phase 2); the barrier
+    // in front of the first phase 2 publishes it.
+    static_assert(kMeanTab == kWave, "lane = count");
+    if (wv == kWalkWaves - 1) s_recip[lane] = mean_recip_entry(lane);
     if (!CMD && wtab != 0u) { // workgroup-uniform
         // lane = window: records of the list in front of window `lane` (window-sorted list); entry NW = all of them
         const uint32_t fw0 = fw_row;
@@ -259,7 +267,7 @@ __global__ __launch_bounds__(kWalkThreads) __attribute__((amdgpu_waves_per_eu(8,
         const int w = g0 + wv;
         float sum[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         uint32_t num[4] = {0u, 0u, 0u, 0u};
-        if (g0 > 0) { // the (mean, count) rows of the previous round lay over planes 0 and 1
+        if (g0 > 0) { // the (sum, count) rows of the previous round lay over planes 0 and 1
             ((float4 *)rplane)[lane] = zero4;
             ((float4 *)rplane)[kWave + lane] = zero4;
         }
@@ -338,9 +346,10 @@ __global__ __launch_bounds__(kWalkThreads) __attribute__((amdgpu_waves_per_eu(8,
                 LDS_FENCE();
             }
         }
-        // the mean is taken HERE, once per (cell, window): 2048 correctly rounded divisions per workgroup and round of windows
-        // instead of 4096 in phase 2 (both lanes of a cell); rows over planes 0 (means) and 1 (counts)
-        ((float4 *)rplane)[lane] = make_float4(fifo_mean(num[0], sum[0]), fifo_mean(num[1], sum[1]), fifo_mean(num[2], sum[2]), fifo_mean(num[3], sum[3]));
+        // (sum, count) of the four cells: rows over planes 0 (sums) and 1 (counts).  The mean is taken in phase 2, behind the barrier
+        // that publishes the reciprocal table: a product and two FMAs per (cell, window) there against a full division expansion
+        // (2 x v_div_scale, v_rcp, 4 FMAs, a product, v_div_fmas, v_div_fixup) here
+        ((float4 *)rplane)[lane] = make_float4(sum[0], sum[1], sum[2], sum[3]);
         ((uint4 *)(rplane + kSubCells))[lane] = make_uint4(num[0], num[1], num[2], num[3]);
         // the 256 thresholds of the leaky transform come to LDS behind phase 2 (requested here, stored in front of its barrier):
         // at the top of the kernel the load's trip was on the path of every wavefront's first barrier
@@ -368,7 +377,7 @@ __global__ __launch_bounds__(kWalkThreads) __attribute__((amdgpu_waves_per_eu(8,
         WPROF(4);
         // ---- phase 2: one cell per lane, the FIFO steps of this round's windows in order
         if (owner) {
-            // (the eight (count, mean) pairs are requested together, in front of the steps: a step that waits for its own pair
+            // (the eight (count, sum) pairs are requested together, in front of the steps: a step that waits for its own pair
             // is an LDS round trip on the workgroup's critical path, eight times)
             uint32_t rn[kWalkWaves];
             float rm[kWalkWaves];
@@ -376,6 +385,23 @@ __global__ __launch_bounds__(kWalkThreads) __attribute__((amdgpu_waves_per_eu(8,
             for (int ws = 0; ws < kWalkWaves; ++ws) {
                 rn[ws] = s_area[ws][kSubCells + tid];
                 rm[ws] = __uint_as_float(s_area[ws][tid]);
+            }
+            // sum -> mean = sum / ((float)n + 1e-8f) (generate_taf.py:27).  No count of the wavefront at or above kMeanTab (all but
+            // the cells of a hot spot): the reciprocals come from the table, their eight loads in flight together, and
+            // mean_by_recip gives the division's bits (taf_mean.h; every reachable sum checked on the CPU).  Otherwise the whole
+            // wavefront divides.
+            uint32_t nmax = rn[0];
+#pragma unroll
+            for (int ws = 1; ws < kWalkWaves; ++ws) nmax = rn[ws] > nmax ? rn[ws] : nmax;
+            if (__ballot(nmax >= (uint32_t)kMeanTab) == 0ull) { // wave-uniform
+                float rr[kWalkWaves];
+#pragma unroll
+                for (int ws = 0; ws < kWalkWaves; ++ws) rr[ws] = s_recip[rn[ws]];
+#pragma unroll
+                for (int ws = 0; ws < kWalkWaves; ++ws) rm[ws] = mean_by_recip(rm[ws], (float)rn[ws], rr[ws]);
+            } else {
+#pragma unroll
+                for (int ws = 0; ws < kWalkWaves; ++ws) rm[ws] = fifo_mean(rn[ws], rm[ws]);
             }
 #pragma unroll
             for (int ws = 0; ws < kWalkWaves; ++ws)
