@@ -206,6 +206,7 @@ SYMBOLS = {
     "frlw_det_bfm_weight_count": (_I, [_I]),
     "frlw_det_add_bfm_stem": (_I, [_P, _I, _I, _I, _I, _P, _I, _I]),
     "frlw_sample_transform_u8": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    "frlw_volume_hand_off_u8": (_I, [C.POINTER(C.c_void_p), _I, _I, _I, _I, _I, _I, _P, _P]),
     "frlw_eval_transform_dt": (_I, [_P, _P, _P, _I64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                    _P, _P, _P]),
     "frlw_coco_workspace_bytes": (_I64, [_I64, _I64, _I64, _I]),

@@ -1,6 +1,7 @@
 // elementwise.hip -- the harness' stand-alone elementwise steps: leaky_transform
 // (generate_taf.py:69-76), uint8 truncation (generate_taf.py:232), nearest resize
-// (generate_eventvolume.py:149).  HBM-bound streaming kernels, grid-stride.
+// (generate_eventvolume.py:149), the loader's sample transform and the volume hand-off that puts a detector batch together
+// from the encoders' uint8 outputs.  HBM-bound streaming kernels, grid-stride.
 
 #include "frlw_common.h"
 
@@ -63,6 +64,51 @@ __global__ void k_sample_transform(const uint8_t *in, int B, int C, int H, int W
     }
 }
 
+// Volume hand-off: the detector batch straight from the encoders' uint8 outputs.  Sample b is C consecutive (h, w) planes
+// behind T.src[b] -- any encoder output, at any byte offset -- and out (B, C, H, W) = nearest_resize(planes, (H, W)) / 255:
+// what k_resize_nearest, a channel slice, a stack and k_sample_transform with default parameters give, in one launch.
+constexpr int kMaxHandOff = 64;
+// The sources of one call, by value (a host array in, no device table to fill; RangeTab of ev_ranges.h does the same).
+struct HandOffTab { const uint8_t *src[kMaxHandOff]; };
+
+// kVec: W % 4 == 0 and out 16-byte aligned -- one item is four consecutive x of one output row, written as one 16-byte store;
+// the row's (b, c, y) and its source row are resolved once per item.  Equal shapes and a 4-byte aligned source address read
+// one word, everything else reads bytes.
+template <bool kVec>
+__global__ __launch_bounds__(256) void k_volume_hand_off(HandOffTab T, int B, int C, int h, int w, int H, int W, float sh,
+                                                         float sw, float *out)
+{
+    const int per_row = kVec ? W / 4 : W;
+    const long long total = (long long)B * C * H * per_row;
+    const bool same = h == H && w == W;
+    for (long long o = blockIdx.x * (long long)blockDim.x + threadIdx.x; o < total;
+         o += (long long)gridDim.x * blockDim.x) {
+        const int xi = (int)(o % per_row), y = (int)((o / per_row) % H);
+        const long long bc = o / ((long long)per_row * H);
+        const int b = (int)(bc / C), c = (int)(bc - (long long)b * C);
+        const int ys = same ? y : nearest_src(y, sh, h);
+        const uint8_t *row = T.src[b] + ((long long)c * h + ys) * w;
+        if (kVec) {
+            const int x = 4 * xi;
+            uint32_t v0, v1, v2, v3;
+            if (same && (((uintptr_t)(row + x)) & 3) == 0) {
+                const uint32_t word = *(const uint32_t *)(row + x);
+                v0 = word & 255u; v1 = (word >> 8) & 255u; v2 = (word >> 16) & 255u; v3 = word >> 24;
+            } else if (same) {
+                v0 = row[x]; v1 = row[x + 1]; v2 = row[x + 2]; v3 = row[x + 3];
+            } else {
+                v0 = row[nearest_src(x, sw, w)]; v1 = row[nearest_src(x + 1, sw, w)];
+                v2 = row[nearest_src(x + 2, sw, w)]; v3 = row[nearest_src(x + 3, sw, w)];
+            }
+            float4 r;
+            r.x = (float)v0 / 255.0f; r.y = (float)v1 / 255.0f; r.z = (float)v2 / 255.0f; r.w = (float)v3 / 255.0f;
+            *(float4 *)(out + 4 * o) = r; // o counts quads in (b, c, y, x / 4) order: 4 * o is the element index
+        } else {
+            out[o] = (float)row[same ? xi : nearest_src(xi, sw, w)] / 255.0f;
+        }
+    }
+}
+
 // Evaluator hand-off (evaluate/evaluator.py:56-63 transform_dt + evaluate/src/io/box_filtering.py:17-39): detection
 // rows [cx, cy, w, h, class, score] in detector pixels -> [t, x, y, w, h, class, score, 0] in sensor pixels (float32
 // like the reference's tensors) and the Prophesee filter mask ts > skip, w^2 + h^2 >= diag^2, w >= min_w, h >= min_h.
@@ -107,6 +153,29 @@ int frlw_sample_transform_u8(const uint8_t *in, int B, int C, int H, int W, cons
     (void)hipGetLastError(); // stale errors of other libraries
     hipLaunchKernelGGL(k_sample_transform, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, in, B, C, H, W,
                        params, out);
+    HIP_TRY(hipGetLastError());
+    return FRLW_OK;
+}
+
+int frlw_volume_hand_off_u8(const uint8_t *const *src, int B, int C, int h, int w, int H, int W, float *out,
+                            frlw_stream_t stream)
+{
+    if (!src || !out || B < 1 || B > kMaxHandOff || C < 1 || h < 1 || w < 1 || H < 1 || W < 1) return FRLW_ERR_ARG;
+    HandOffTab T;
+    for (int b = 0; b < kMaxHandOff; ++b) {
+        T.src[b] = src[b < B ? b : B - 1]; // the unused entries repeat the last source: no stray pointer travels
+        if (!T.src[b]) return FRLW_ERR_ARG;
+    }
+    const bool vec = W % 4 == 0 && ((uintptr_t)out & 15) == 0;
+    const long long items = (long long)B * C * H * (vec ? W / 4 : W);
+    const float sh = (float)h / (float)H, sw = (float)w / (float)W;
+    (void)hipGetLastError(); // stale errors of other libraries
+    if (vec)
+        hipLaunchKernelGGL(k_volume_hand_off<true>, dim3(grid_for(items, 256)), dim3(256), 0, (hipStream_t)stream, T, B,
+                           C, h, w, H, W, sh, sw, out);
+    else
+        hipLaunchKernelGGL(k_volume_hand_off<false>, dim3(grid_for(items, 256)), dim3(256), 0, (hipStream_t)stream, T,
+                           B, C, h, w, H, W, sh, sw, out);
     HIP_TRY(hipGetLastError());
     return FRLW_OK;
 }

@@ -4,7 +4,8 @@
 same checkpoint files and dict layout (``saveCheckpoint`` :198-210, ``loadCheckpoint`` :155-165), so checkpoints
 interchange with the reference's -- pinned by tests/golden/entry_points.json.
 
-Data: with ``--bbox_path`` / ``--data_path`` the pre-encoded ``uint8`` files of the ``generate_*.py`` commands are read by
+Data: with ``--raw_dir`` / ``--representation`` (test.py) the test split is encoded from the recordings on the GPU and handed to the
+detector without files (``frlw_evd_amd.recording_dataset``); with ``--bbox_path`` / ``--data_path`` the pre-encoded ``uint8`` files of the ``generate_*.py`` commands are read by
 ``frlw_evd_amd.dataset`` (the reference's dataset classes and ``Loader``: uint8 batches over PCIe, the sample transform as
 one kernel on the GPU).  A run without them draws SYNTHETIC event streams and encodes them on the GPU every step
 (``e2e.SyntheticTafSource``), which is BASELINE.json's config 5.  The evaluator hand-off is the real one
@@ -93,9 +94,15 @@ class basicExp:
         ``--data_path``; the training split goes through a DistributedSampler like the reference's."""
         from .dataset import Loader
         s = self.settings
-        if s.bbox_path is None or s.data_path is None:
+        raw_dir = getattr(s, "raw_dir", None)
+        if raw_dir is not None and not test_only:
+            raise ValueError("--raw_dir evaluates the test split; training reads the files of the generate_*.py commands")
+        if raw_dir is None and (s.bbox_path is None or s.data_path is None):
             raise ValueError("--bbox_path and --data_path come together (omit both for the synthetic GPU-encoded run)")
-        if test_only:
+        if raw_dir is not None:
+            val = self.val_loader = self._recording_loader()
+            self.object_classes = val.object_classes
+        elif test_only:
             val = self._dataset("test", False, False)
             self.object_classes = val.object_classes
             self.val_loader = Loader(val, batch_size=s.batch_size, device=s.gpu_device, num_workers=s.num_cpu_workers,
@@ -116,6 +123,29 @@ class basicExp:
             print(f"test_loader_len: {len(self.val_loader)}")
         self.nr_val_epochs = len(self.val_loader)
         self.ori_width, self.ori_height = val.width, val.height
+
+    _recording_kinds = ("ev", "eci", "sae")   # what propheseeDataset reads; the TAF experiments: ("taf",)
+
+    def _recording_loader(self):
+        """``--raw_dir``: the test split encoded from the recordings (``recording_dataset.RecordingLoader``) in place of the
+        dataset + ``Loader`` over a command's files.  A representation the experiment's dataset class does not read ends the run."""
+        from .recording_dataset import RecordingLoader, parse_representation, representation_channels
+        s = self.settings
+        try:
+            kind, _ = parse_representation(s.representation, s.dataset_name)
+        except ValueError as e:
+            raise SystemExit(f"--representation: {e}")
+        if kind not in self._recording_kinds:
+            fits = "taf" if "taf" in self._recording_kinds else "EventVolume<tw>, EventCountImage<N> or SurfaceOfActiveEvents<lambda>"
+            other = "taf, taf_bfm or yolox_taf_bfm" if kind == "taf" else "basic or yolox"
+            raise SystemExit(f"--representation {s.representation} does not fit this --exp_type: it takes {fits} "
+                             f"(--exp_type {other} reads {s.representation})")
+        try:
+            representation_channels(kind, s.event_volume_bins)
+        except ValueError as e:
+            raise SystemExit(f"--representation {s.representation}: {e}")
+        return RecordingLoader(s.bbox_path, s.raw_dir, s.representation, s.dataset_name, s.input_img_size, s.img_size,
+                               s.event_volume_bins, "test", s.batch_size, s.gpu_device, False)
 
     _clip_train = True   # basicExp passes settings.clipping to the training split (core/exp.py:70), the TAF exps False (:414)
     _shard_val = True    # basicExp gives the validation split a DistributedSampler (core/exp.py:87), the TAF exps do not (:430-435)
@@ -304,6 +334,7 @@ class basicExp:
 
 class tafExp(basicExp):
     """core/exp.py:393-465: the AED detector on ``propheseeTafDataset`` (bins4 + bins8 files of ``generate_taf.py``)."""
+    _recording_kinds = ("taf",)
     _clip_train = False
     _shard_val = False
 
@@ -342,6 +373,7 @@ class yoloxtafBFM(yolox):
         from .yolox.bfm import Temporal_Active_Focus_connect
         self.input_layer = Temporal_Active_Focus_connect
 
+    _recording_kinds = ("taf",)
     _clip_train = False
     _shard_val = False
 

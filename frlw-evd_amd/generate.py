@@ -9,6 +9,10 @@ scripts wrote on a fabricated dataset (tests/golden/make_golden_harness.py).
 Each ``*_td.dat`` file goes to HBM ONCE as raw 8-byte records (``DatFile.to_device``); every label is a record range of that
 tensor: bit-unpacking, window selection, f64 time normalisation, the coordinate down-scale, encode, nearest resize and uint8
 quantisation all run on the device, only the finished uint8 file comes back.
+
+The per-file body of every command is a generator of ``(label_time, uint8 volume on the GPU at the encode shape)`` in label order
+(``eci_volumes``, ``ev_volumes``, ``sae_volumes``, ``taf_volumes``); the commands are writers over them, and
+``recording_dataset.RecordingLoader`` hands the same volumes to the detector without the files.
 """
 from __future__ import annotations
 
@@ -70,27 +74,49 @@ def _write(u8, enc_shape, target, path):
 
 
 # ---- generate_eventcountimage.py:66-185 ---------------------------------------------------------------------------------
+ECI_EVENTS_WINDOWS = {"gen4": [400000, 800000, 1200000], "gen1": [50000, 100000, 200000]}
+
+
+def eci_events_windows(dataset):
+    return ECI_EVENTS_WINDOWS["gen4" if dataset == "gen4" else "gen1"]
+
+
+def eci_volumes(f_event, dat, label_times, enc, xmap, ymap, events_windows, select=None):
+    """The Event Count Images of one file, in label order: yields ``(label_time, [volume per window of events_windows])``, or
+    with ``select=N`` (one of ``events_windows``) ``(label_time, volume of window N)`` -- uint8 (2, h, w) at the encode shape, views
+    of the encoder's output on the GPU.  The slices always come from the full window list (the memory the harness keeps depends
+    on the largest).  Every (label, window) is a record range of ``dat`` -- the windows of a label are nested, they end at the same
+    record -- so the file's ranges go through the batched encoder, up to 64 per call, instead of one call and one
+    synchronisation each."""
+    if select is not None and select not in events_windows:
+        raise ValueError(f"select: one of {list(events_windows)}")
+    windows = list(events_windows) if select is None else [select]
+    jobs = []   # (lo, hi, label time)
+    for sl in dat_io.eci_label_slices(f_event, label_times, events_windows):
+        for n in windows:
+            jobs.append((max(sl["tail_start"], sl["end_count"] - n), sl["end_count"], sl["label_time"]))
+    held = []   # the windows of a label may lie in two calls
+    for j0 in range(0, len(jobs), er._lib.MAX_SEQUENCES):
+        part = jobs[j0:j0 + er._lib.MAX_SEQUENCES]
+        _, u8 = er.encode_eci_batch(dat, [(lo, hi) for lo, hi, _ in part], enc, want_f32=False, want_u8=True, xmap=xmap, ymap=ymap)
+        for b, (_, _, label_time) in enumerate(part):
+            held.append(u8[b])
+            if len(held) == len(windows):
+                yield label_time, (held if select is None else held[0])
+                held = []
+
+
 def generate_eventcountimage(raw_dir, label_dir, target_dir, dataset="gen4", device="cuda"):
-    events_windows = [400000, 800000, 1200000] if dataset == "gen4" else [50000, 100000, 200000]
+    events_windows = eci_events_windows(dataset)
     _, target, enc, xmap, ymap = _geometry(dataset, device)
     os.makedirs(target_dir, exist_ok=True)
     n_files = 0
     for mode, name, event_file, bbox_file in _sequences(raw_dir, label_dir):
         f_event = dat_io.DatFile(event_file)
         dat = f_event.to_device(device=device)
-        # every (label, window) of the file is a record range of `dat` -- the three windows of a label are nested, they end at the
-        # same record -- so the file's ranges go through the batched encoder, up to 64 per call, instead of one call and one
-        # synchronisation each
-        jobs = []   # (lo, hi, output path)
-        for sl in dat_io.eci_label_slices(f_event, read_label_times(bbox_file), events_windows):
-            for n in events_windows:
-                lo = max(sl["tail_start"], sl["end_count"] - n)
-                jobs.append((lo, sl["end_count"], os.path.join(target_dir, f"EventCountImage{n}", mode, f"{name}_{sl['label_time']}.npy")))
-        for j0 in range(0, len(jobs), er._lib.MAX_SEQUENCES):
-            part = jobs[j0:j0 + er._lib.MAX_SEQUENCES]
-            _, u8 = er.encode_eci_batch(dat, [(lo, hi) for lo, hi, _ in part], enc, want_f32=False, want_u8=True, xmap=xmap, ymap=ymap)
-            for b, (_, _, path) in enumerate(part):
-                _write(u8[b], enc, target, path)
+        for label_time, vols in eci_volumes(f_event, dat, read_label_times(bbox_file), enc, xmap, ymap, events_windows):
+            for n, u8 in zip(events_windows, vols):
+                _write(u8, enc, target, os.path.join(target_dir, f"EventCountImage{n}", mode, f"{name}_{label_time}.npy"))
                 n_files += 1
     return n_files
 
@@ -141,6 +167,32 @@ def _eventvolume_loop(dat, part, enc, tw, bins, xmap, ymap):
             for lo, hi, end, _ in part]
 
 
+def ev_volumes(f_event, dat, label_times, enc, xmap, ymap, select, time_windows=EV_TIME_WINDOWS, bins=5, slices=None):
+    """The Event Volumes of one file for the time window ``select`` (one of ``time_windows``), in label order: yields
+    ``(label_time, uint8 (2 * bins, h, w))`` at the encode shape on the GPU.  The slices always come from the full
+    ``time_windows`` (``start_count`` and the 10 M cap depend on the largest); ``slices``: ``list(dat_io.ev_label_slices(...))``
+    when the caller has it already.  The label slices of a file overlap (each reaches ``max(time_windows)`` back), so a window
+    is a record RANGE of ``dat``: the ranges go through ``encode_ev_ranges``, up to 64 per call, instead of one call and one
+    synchronisation each; a part the ranged path does not take runs per window."""
+    tw = int(select)
+    if tw not in time_windows:
+        raise ValueError(f"select: one of {list(time_windows)}")
+    if slices is None:
+        slices = list(dat_io.ev_label_slices(f_event, label_times, time_windows))
+    jobs = [job[:3] + (sl["label_time"],) for job, sl in zip(ev_jobs(slices, tw, "", f_event._t), slices)]
+    max_windows = er.ev_ranges_max_windows(enc, tw)
+    for part in ev_parts(jobs, max(max_windows, 1)):
+        try:
+            if max_windows == 0:
+                raise NotImplementedError
+            _, u8 = er.encode_ev_ranges(dat, [(lo, hi) for lo, hi, _, _ in part], enc, [end for _, _, end, _ in part], tw, bins,
+                                        want_f32=False, want_u8=True, xmap=xmap, ymap=ymap)
+        except NotImplementedError:
+            u8 = _eventvolume_loop(dat, part, enc, tw, bins, xmap, ymap)
+        for b, (_, _, _, label_time) in enumerate(part):
+            yield label_time, u8[b]
+
+
 def generate_eventvolume(raw_dir, label_dir, target_dir, dataset="gen1", device="cuda"):
     time_windows = EV_TIME_WINDOWS
     bins = 5
@@ -150,23 +202,11 @@ def generate_eventvolume(raw_dir, label_dir, target_dir, dataset="gen1", device=
     for mode, name, event_file, bbox_file in _sequences(raw_dir, label_dir):
         f_event = dat_io.DatFile(event_file)
         dat = f_event.to_device(device=device)
-        # the label slices of a file overlap (each reaches max(time_windows) back), so a window is a record RANGE of `dat`: the
-        # ranges of one time window go through encode_ev_ranges, up to 64 per call, instead of one call and one synchronisation each
         slices = list(dat_io.ev_label_slices(f_event, read_label_times(bbox_file), time_windows))
         for tw in time_windows:
-            jobs = ev_jobs(slices, tw, os.path.join(target_dir, f"EventVolume{tw}", mode, name), f_event._t)
-            max_windows = er.ev_ranges_max_windows(enc, tw)
-            for part in ev_parts(jobs, max(max_windows, 1)):
-                try:
-                    if max_windows == 0:
-                        raise NotImplementedError
-                    _, u8 = er.encode_ev_ranges(dat, [(lo, hi) for lo, hi, _, _ in part], enc, [end for _, _, end, _ in part], tw, bins,
-                                                want_f32=False, want_u8=True, xmap=xmap, ymap=ymap)
-                except NotImplementedError:
-                    u8 = _eventvolume_loop(dat, part, enc, tw, bins, xmap, ymap)
-                for b, (_, _, _, path) in enumerate(part):
-                    _write(u8[b], enc, target, path)
-                    n_files += 1
+            for label_time, u8 in ev_volumes(f_event, dat, None, enc, xmap, ymap, tw, time_windows, bins, slices):
+                _write(u8, enc, target, os.path.join(target_dir, f"EventVolume{tw}", mode, f"{name}_{label_time}.npy"))
+                n_files += 1
     return n_files
 
 
@@ -194,6 +234,27 @@ def sae_parts(steps, max_steps=er._lib.MAX_SEQUENCES):
     return [steps[i:i + max_steps] for i in range(0, len(steps), max_steps)]
 
 
+def sae_volumes(f_event, dat, label_times, mode, enc, xmap, ymap, lamdas=SAE_LAMDAS, select=None):
+    """The Surfaces of Active Events of one file, in label order: yields ``(label_time, uint8 (2 * len(lamdas), h, w))`` at the
+    encode shape on the GPU -- channels ``2j, 2j + 1`` belong to ``lamdas[j]`` -- or with ``select=lam`` (one of ``lamdas``)
+    only those two channels (a view).  The chain always runs all of ``sae_steps(..., mode)`` with all of ``lamdas``: the labels
+    of a file are a chain -- the per-pixel memory goes from label to label -- which ``encode_sae_chain`` runs as one call per 64
+    steps; the memory is carried from part to part and starts anew with every file."""
+    if select is not None and select not in lamdas:
+        raise ValueError(f"select: one of {list(lamdas)}")
+    memory = None
+    steps = sae_steps(dat_io.sae_label_slices(f_event, label_times), mode)
+    for part in sae_parts(steps):
+        _, u8, memory = er.encode_sae_chain(dat, part, enc, lamdas, memory, want_f32=False, want_u8=True, xmap=xmap, ymap=ymap)
+        emitted = 0
+        for _, _, label_time, _, emit in part:
+            if not emit:
+                continue
+            vol = u8[emitted].view(len(lamdas), 2, enc[0], enc[1])
+            emitted += 1
+            yield label_time, (vol.view(2 * len(lamdas), enc[0], enc[1]) if select is None else vol[list(lamdas).index(select)])
+
+
 def generate_surfaceofactiveevents(raw_dir, label_dir, target_dir, dataset="gen1", device="cuda"):
     lamdas = SAE_LAMDAS
     _, target, enc, xmap, ymap = _geometry(dataset, device)
@@ -202,21 +263,10 @@ def generate_surfaceofactiveevents(raw_dir, label_dir, target_dir, dataset="gen1
     for mode, name, event_file, bbox_file in _sequences(raw_dir, label_dir):
         f_event = dat_io.DatFile(event_file)
         dat = f_event.to_device(device=device)
-        # the labels of a file are a chain -- the per-pixel memory goes from label to label -- which encode_sae_chain runs as one
-        # call per 64 steps; the memory is carried from part to part and starts anew with every file
-        memory = None
-        steps = sae_steps(dat_io.sae_label_slices(f_event, read_label_times(bbox_file)), mode)
-        for part in sae_parts(steps):
-            _, u8, memory = er.encode_sae_chain(dat, part, enc, lamdas, memory, want_f32=False, want_u8=True, xmap=xmap, ymap=ymap)
-            emitted = 0
-            for _, _, label_time, _, emit in part:
-                if not emit:
-                    continue
-                vol = u8[emitted].view(len(lamdas), 2, enc[0], enc[1])
-                emitted += 1
-                for j, lam in enumerate(lamdas):
-                    _write(vol[j], enc, target, os.path.join(target_dir, f"SurfaceOfActiveEvents{lam}", mode, f"{name}_{label_time}.npy"))
-                    n_files += 1
+        for label_time, vol in sae_volumes(f_event, dat, read_label_times(bbox_file), mode, enc, xmap, ymap, lamdas):
+            for j, lam in enumerate(lamdas):
+                _write(vol[2 * j:2 * j + 2], enc, target, os.path.join(target_dir, f"SurfaceOfActiveEvents{lam}", mode, f"{name}_{label_time}.npy"))
+                n_files += 1
     return n_files
 
 
@@ -258,8 +308,46 @@ def taf_chains(slices, last_time_of, events_window_abin=10000, max_snapshots=er.
     return chains
 
 
+TAF_WINDOW_US, TAF_BINS, TAF_MIN_EVENT_COUNT = 10000, 8, 50000000   # generate_taf.py's events_window_abin, K, min_event_count
+
+
+def taf_chain_volumes(f_event, dat, label_times, enc, xmap, ymap):
+    """The TAF volumes of one file, one encoder call at a time: yields ``(chain, uint8 (len(chain), K, 2, h, w))`` at the encode
+    shape on the GPU, ``chain`` the ``dat_io.taf_label_slices`` dicts of the call's labels in label order.  A run of labels on
+    one window grid is one ``encode_taf_chain`` call -- one partition, one tile launch, one synchronisation -- instead of one
+    ``encode_taf_label`` call each; a label alone in its chain takes the per-label call."""
+    events_window_abin, K = TAF_WINDOW_US, TAF_BINS
+    state, stale = None, 0
+    slices = list(dat_io.taf_label_slices(f_event, label_times, events_window_abin, K, TAF_MIN_EVENT_COUNT))
+    chains = taf_chains(slices, lambda sl: int(f_event._t[sl["end_count"] - 1]) if sl["end_count"] > sl["start_count"] else None,
+                        events_window_abin)
+    for chain in chains:
+        sl = chain[0]
+        if sl["fresh"]:
+            state = torch.full((enc[0], enc[1], 2, K), -6000.0, device=dat.device)   # :205-209
+        # a label that rounds onto the previous one has no window (:181): the reference's `volume` is then STALE -- the
+        # previous label's already transformed volume goes through leaky_transform again (:226-227); `stale` counts how
+        # many such labels precede this one in a row
+        stale = stale + 1 if sl["bins"] <= 0 else 0
+        if len(chain) == 1:
+            vols = er.encode_taf_label(dat[sl["start_count"]:sl["end_count"]], enc, state, sl["start_time"], events_window_abin,
+                                       sl["bins"], K, flip_k=True, xmap=xmap, ymap=ymap, stale_transforms=max(stale - 1, 0))[None]
+        else:
+            vols = er.encode_taf_chain(dat[sl["start_count"]:chain[-1]["end_count"]], enc, state, sl["start_time"],
+                                       events_window_abin, [c["bins"] for c in chain], K, flip_k=True, xmap=xmap, ymap=ymap)
+        yield chain, vols
+
+
+def taf_volumes(f_event, dat, label_times, enc, xmap, ymap):
+    """``taf_chain_volumes`` label by label: yields ``(label_time, uint8 (K, 2, h, w))``, newest slot first -- planes ``[:K]`` are
+    the ``bins{K/2}`` file, ``[K:]`` the ``bins{K}`` file.  No selection: the FIFO is one state."""
+    for chain, vols in taf_chain_volumes(f_event, dat, label_times, enc, xmap, ymap):
+        for c, vol in zip(chain, vols):
+            yield c["label_time"], vol
+
+
 def generate_taf(raw_dir, label_dir, target_dir, dataset="gen4", device="cuda"):
-    events_window_abin, K, min_event_count = 10000, 8, 50000000
+    K = TAF_BINS
     _, target, enc, xmap, ymap = _geometry(dataset, device)
     target_dir = os.path.join(target_dir, "taf")
     os.makedirs(target_dir, exist_ok=True)
@@ -268,27 +356,8 @@ def generate_taf(raw_dir, label_dir, target_dir, dataset="gen4", device="cuda"):
         os.makedirs(os.path.join(target_dir, mode), exist_ok=True)
         f_event = dat_io.DatFile(event_file)
         dat = f_event.to_device(device=device)
-        state, stale = None, 0
-        slices = list(dat_io.taf_label_slices(f_event, read_label_times(bbox_file), events_window_abin, K, min_event_count))
-        # a run of labels on one window grid is one encode_taf_chain call -- one partition, one tile launch, one synchronisation
-        # -- instead of one encode_taf_label call each; a label alone in its chain takes the per-label call as before
-        chains = taf_chains(slices, lambda sl: int(f_event._t[sl["end_count"] - 1]) if sl["end_count"] > sl["start_count"] else None,
-                            events_window_abin)
-        for chain in chains:
-            sl = chain[0]
-            if sl["fresh"]:
-                state = torch.full((enc[0], enc[1], 2, K), -6000.0, device=device)   # :205-209
-            # a label that rounds onto the previous one has no window (:181): the reference's `volume` is then STALE -- the
-            # previous label's already transformed volume goes through leaky_transform again (:226-227); `stale` counts how
-            # many such labels precede this one in a row
-            stale = stale + 1 if sl["bins"] <= 0 else 0
-            if len(chain) == 1:
-                vols = er.encode_taf_label(dat[sl["start_count"]:sl["end_count"]], enc, state, sl["start_time"], events_window_abin,
-                                           sl["bins"], K, flip_k=True, xmap=xmap, ymap=ymap, stale_transforms=max(stale - 1, 0))[None]
-            else:
-                vols = er.encode_taf_chain(dat[sl["start_count"]:chain[-1]["end_count"]], enc, state, sl["start_time"],
-                                           events_window_abin, [c["bins"] for c in chain], K, flip_k=True, xmap=xmap, ymap=ymap)
-            if tuple(enc) != tuple(target):
+        for chain, vols in taf_chain_volumes(f_event, dat, read_label_times(bbox_file), enc, xmap, ymap):
+            if tuple(enc) != tuple(target):   # one resize and one copy to the host per call
                 vols = er.resize_nearest(vols.reshape(len(chain) * 2 * K, enc[0], enc[1]), target).reshape(len(chain), K, 2, target[0], target[1])
             vols = vols.cpu().numpy()
             for host, c in zip(vols, chain):

@@ -70,12 +70,8 @@ class StreamDetector:
     def hand_off(self, u8, enc):
         """uint8 volumes (S, K, 2, h, w) at the encode shape -> detector input (S, C, H, W, 1) float32: the channels the dataset
         class reads for ``input_bins``, nearest resize to ``img_size`` when the shapes differ, ``/255``."""
-        S = u8.shape[0]
-        vol = u8.reshape(S, 2 * self.K, enc[0], enc[1])[:, :self.channels].contiguous()
-        if tuple(enc) != self.img_size:
-            vol = er.resize_nearest(vol.reshape(S * self.channels, enc[0], enc[1]), self.img_size)
-        vol = vol.reshape(S, self.channels, self.img_size[0], self.img_size[1])
-        return transforms.transform_images(vol, [transforms.SampleParams()] * S)[..., 0]
+        u8 = u8.contiguous()
+        return transforms.hand_off([u8[s] for s in range(u8.shape[0])], self.channels, enc, self.img_size)[..., 0]
 
     def boxes(self, outputs, stamps):
         """Detections of one batch (``model.detect``'s list) -> list of (n_i, 8) float32 rows [t, x, y, w, h, class, confidence,

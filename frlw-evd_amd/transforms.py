@@ -125,3 +125,42 @@ def transform_images(u8, params, out=None):
     _lib.check(lib.frlw_sample_transform_u8(u8.data_ptr(), B, Cc, H, W, tab_d.data_ptr(), out.data_ptr(),
                                             torch.cuda.current_stream(u8.device).cuda_stream), "frlw_sample_transform_u8")
     return out
+
+
+MAX_HAND_OFF = 64  # samples one frlw_volume_hand_off_u8 launch takes (its pointer table travels by value)
+
+
+def hand_off(sources, C, src_shape, out_shape, out=None):
+    """A detector batch from uint8 volumes that lie in different encoder outputs: ``sources`` is a list of B (1..64) uint8
+    tensors on the GPU, each holding at least ``C`` contiguous ``src_shape`` planes from its ``data_ptr()`` (a view
+    into a chain's snapshots, a channel slice of a larger volume, at any byte offset) -> (B, C, H, W, 1, 1) float32 =
+    ``nearest_resize(planes, out_shape) / 255``, byte-equal to ``resize_nearest`` + ``transform_images`` with default
+    parameters.  One launch, no intermediate, no device table; no CPU fallback."""
+    import ctypes
+
+    import torch
+
+    from . import _lib
+    lib = _lib.load()
+    B = len(sources)
+    h, w = int(src_shape[0]), int(src_shape[1])
+    H, W = int(out_shape[0]), int(out_shape[1])
+    Cn = int(C)
+    if not 1 <= B <= MAX_HAND_OFF:
+        raise ValueError(f"hand_off takes 1..{MAX_HAND_OFF} samples per call")
+    if Cn < 1 or min(h, w, H, W) < 1:
+        raise ValueError("hand_off needs positive sizes")
+    device = sources[0].device
+    for b, s in enumerate(sources):
+        if not (s.is_cuda and s.dtype == torch.uint8 and s.is_contiguous() and s.device == device):
+            raise ValueError(f"sample {b}: a contiguous uint8 tensor on the GPU is needed")
+        if s.numel() < Cn * h * w:
+            raise ValueError(f"sample {b}: {s.numel()} bytes, {Cn} planes of {h} x {w} need {Cn * h * w}")
+    if out is None:
+        out = torch.empty((B, Cn, H, W, 1, 1), dtype=torch.float32, device=device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * Cn * H * W):
+        raise ValueError("out: a contiguous float32 tensor of B * C * H * W elements on the GPU")
+    table = (ctypes.c_void_p * B)(*[s.data_ptr() for s in sources])
+    _lib.check(lib.frlw_volume_hand_off_u8(table, B, Cn, h, w, H, W, out.data_ptr(),
+                                           torch.cuda.current_stream(device).cuda_stream), "frlw_volume_hand_off_u8")
+    return out

@@ -791,6 +791,16 @@ int frlw_yolox_loss_bwd(const float *const *raw, const int32_t *h, const int32_t
 int frlw_sample_transform_u8(const uint8_t *in, int B, int C, int H, int W, const int32_t *params, float *out,
                              frlw_stream_t stream);
 
+/* Volume hand-off: a detector batch from uint8 volumes that lie in different encoder outputs, in one launch.
+ * src: HOST array of B (1..64) device pointers; src[b] is the first of C consecutive (h, w) uint8 planes of sample b, at any
+ * byte address.  The pointers travel to the kernel by value: no device table, no copy, capturable.
+ * out (B, C, H, W) f32: out[b][c][y][x] = (float)src[b][c][ys][xs] / 255.0f with the nearest rule of frlw_resize_nearest_u8
+ * (ys = min(floor(y * (float)h / (float)H), h - 1), xs likewise) -- byte-equal to frlw_resize_nearest_u8 followed by
+ * frlw_sample_transform_u8 with {H, W, 0, 0, 0} rows.  B outside 1..64, a non-positive size or a NULL pointer:
+ * FRLW_ERR_ARG, nothing is written. */
+int frlw_volume_hand_off_u8(const uint8_t *const *src, int B, int C, int h, int w, int H, int W, float *out,
+                            frlw_stream_t stream);
+
 /* Evaluator hand-off for the detections of a batch (evaluate/evaluator.py:56-63 transform_dt, and the mask of
  * evaluate/src/io/box_filtering.py:17-39): n packed rows [cx, cy, w, h, class, score] (detector pixels) ->
  * out (n, 8) f32 [t, x, y, w, h, class, score, 0] (sensor pixels; t = timestamps[img_of_row[i]]) and

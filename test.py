@@ -2,8 +2,11 @@
 """Evaluation entry point with the reference's command line (test.py:9-52): same flags, process-group init and
 ``Setting_test`` -> ``yolox(settings).test()`` dispatch; ``--resume_exp E`` loads ``<log_path>E/checkpoints/best_epoch.pth``
 (a checkpoint written by this build or by the reference: same dict layout and parameter names), ``--record True`` writes
-``summarise.npz``.  Without ``--data_path`` / ``--bbox_path`` the run is synthetic (see train.py); the detections go
-through the gfx950 engine (decode + NMS on device) and the evaluator hand-off."""
+``summarise.npz``.  ``--raw_dir DIR --representation NAME`` (instead of ``--data_path``) evaluates straight from the recordings:
+the test split's label volumes are encoded on the GPU as the ``generate_*.py`` command of ``NAME`` (the README's DATA_DIR: ``taf``,
+``EventVolume250000``, ...) would write them and handed to the detector without files -- same boxes, same score.  Without
+``--data_path`` / ``--bbox_path`` / ``--raw_dir`` the run is synthetic (see train.py); the detections go through the gfx950 engine
+(decode + NMS on device) and the evaluator hand-off."""
 import argparse
 import os
 import sys
@@ -21,7 +24,10 @@ def build_parser():
     parser.add_argument("--record", type=bool)  # summarise.npz under log_path for visualisation / motion-level evaluation
     parser.add_argument("--dataset", default="gen1")
     parser.add_argument("--bbox_path")
-    parser.add_argument("--data_path")
+    source = parser.add_mutually_exclusive_group()
+    source.add_argument("--data_path")
+    source.add_argument("--raw_dir")          # "train, val, test" level directory of the recordings (<mode>/<seq>_td.dat)
+    parser.add_argument("--representation")   # with --raw_dir: the directory name the offline command would have written
     parser.add_argument("--event_volume_bins", type=int, default=5)
     parser.add_argument("--batch_size", type=int, default=1)
     parser.add_argument("--num_cpu_workers", type=int, default=-1)
@@ -30,9 +36,22 @@ def build_parser():
     return parser
 
 
+def parse_args(argv=None):
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.raw_dir is not None:
+        if args.representation is None:
+            parser.error("--raw_dir needs --representation (taf, EventVolume<tw>, EventCountImage<N>, SurfaceOfActiveEvents<lambda>)")
+        if args.bbox_path is None:   # the README keeps recordings and annotations in one tree
+            args.bbox_path = args.raw_dir
+    elif args.representation is not None:
+        parser.error("--representation goes with --raw_dir")
+    return args
+
+
 def main(argv=None):
     import train as train_entry
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     cls = train_entry.pick_experiment(args.exp_type)
     train_entry.init_distributed(args)
     from frlw_evd_amd.settings import Setting_test
